@@ -49,6 +49,9 @@ def parse():
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configs")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (rank 0, e.g. bench_outputs/; "
+                         "float32 / float64, at most 64 MB: larger outputs as a fixed, seeded sample of utterances)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="preflight: bring the ranks up, check one all-gather, run no workload (needs no GPU "
                          "with PDT_BENCH_BACKEND=gloo)")
@@ -120,6 +123,33 @@ def peaky_logits(T, N, V, device, seed, chunk=64):
         peak = torch.randint(0, V + 1, (part.shape[0], N, 1), device=device, generator=g)
         part.scatter_add_(2, peak, torch.full((part.shape[0], N, 1), 12.0, device=device))
     return lg
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """Write `outs` ({name: (tensor, utterance axis)}) as path/<name>.npy, as float64 if the tensor is float64
+    and float32 otherwise (integer outputs here are token ids, lengths and counts, exact in float32).  Every
+    array gets an equal share of DUMP_BYTES; one that exceeds its share keeps a seeded random subset of its
+    utterances, in ascending order, so that two runs with the same arguments write the same sample."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outs))
+    total = 0
+    for name, (x, axis) in outs.items():
+        dt = torch.float64 if x.dtype == torch.float64 else torch.float32
+        n = x.shape[axis]
+        utt_bytes = (x.numel() // max(1, n)) * (8 if dt == torch.float64 else 4)
+        if n * utt_bytes > share:
+            keep = max(1, share // max(1, utt_bytes))
+            idx = np.sort(np.random.default_rng(0x5EED00D0).permutation(n)[:keep])
+            x = x.index_select(axis, torch.from_numpy(idx).to(x.device))
+        a = x.detach().to(dt).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_BYTES:
+            raise SystemExit("bench.py: --dump-outputs would write more than {} bytes".format(DUMP_BYTES))
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
 
 
 def event_ms(fn, reps=5, warm=2):
@@ -699,6 +729,8 @@ def run_rank(args):
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.gpus != world:
         raise SystemExit("--gpus {} but WORLD_SIZE={}".format(args.gpus, world))
+    if args.steps < 1 and not args.rendezvous_only:
+        raise SystemExit("--steps must be positive")
     if args.rendezvous_only:
         return rendezvous_only(args, world, rank)
     local_rank = local_rank % max(1, torch.cuda.device_count())
@@ -754,7 +786,8 @@ def run_rank(args):
     def gather_check(got, want):
         return agree(torch.equal(got, want))
 
-    def step(events=None):
+    def step(events=None, outs=None):
+        """One step; `outs`, if given, receives what the step computed (utterance axis of each output)."""
         k = 0
 
         def mark():
@@ -766,17 +799,25 @@ def run_rank(args):
         mark()
         er = F.error_rate(ref, hyp, warn=False)
         mark()
-        F.prefix_error_rates(ref, hyp, warn=False)
+        per = F.prefix_error_rates(ref, hyp, warn=False)
         mark()
         oc = F.optimal_completion(ref, hyp, warn=False)
         C_seen[0] = oc.shape[-1]
         mark()
+        dec = None
         if have_decode:
-            F.ctc_prefix_search(logits, args.beam)
+            dec = F.ctc_prefix_search(logits, args.beam)
             mark()
         if world > 1:
             gather(er)
             mark()
+        if outs is not None:
+            outs.update(error_rate=(er, 0), prefix_error_rates=(per, 1), optimal_completion=(oc, 1))
+            if dec is not None:
+                outs.update(ctc_prefix_search_y=(dec[0], 1), ctc_prefix_search_y_lens=(dec[1], 0),
+                            ctc_prefix_search_y_probs=(dec[2], 0))
+            if world > 1:
+                outs["error_rate_gathered"] = (gathered, 0)
         return er
 
     for _ in range(args.warmup):
@@ -797,10 +838,11 @@ def run_rank(args):
     ]
     if world > 1:
         dist.barrier()
+    last_outs = {} if args.dump_outputs else None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(args.steps):
-        step(evs[s])
+        step(evs[s], last_outs if s == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -871,6 +913,9 @@ def run_rank(args):
             print("bench.py: " + msg, file=sys.stderr, flush=True)
 
     say("timed region done: {:.3f} ms per step".format(dt / args.steps * 1e3))
+    if last_outs is not None and rank == 0:
+        nbytes = dump_outputs(args.dump_outputs, last_outs)
+        say("outputs of the last timed step: {} arrays, {} bytes in {}".format(len(last_outs), nbytes, args.dump_outputs))
     extra = None
     if not args.no_extra and have_decode:
         # (one stderr line per configuration as it finishes, and `config_summary` as the LAST key of the

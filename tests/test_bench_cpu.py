@@ -66,3 +66,33 @@ def test_cpu_baseline_record():
     for op in op_ms:
         assert rec["per_op"][op]["reps"] >= 5
         assert rec["threads_8"]["per_op"][op]["utt_per_s_median"] > 0
+
+
+def test_dump_outputs_fits_the_budget_and_repeats(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+
+    import bench
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 3 * 4096)
+    g = torch.Generator().manual_seed(1)
+    outs = {"small": (torch.rand((100,), generator=g), 0),
+            "wide": (torch.randint(0, 50, (9, 200, 3), generator=g), 1),
+            "f64": (torch.rand((7, 300), dtype=torch.float64, generator=g), 1)}
+    paths = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        total = bench.dump_outputs(str(d), outs)
+        assert total <= bench.DUMP_BYTES
+        assert sorted(p.name for p in d.iterdir()) == ["f64.npy", "small.npy", "wide.npy"]
+        paths.append(d)
+    small, wide, f64 = (np.load(paths[0] / (n + ".npy")) for n in ("small", "wide", "f64"))
+    assert small.dtype == np.float32 and np.array_equal(small, outs["small"][0].numpy())
+    # over its share of the budget: a subset of the utterances, in order, values exact
+    assert wide.dtype == np.float32 and wide.shape[0] == 9 and wide.shape[2] == 3 and 0 < wide.shape[1] < 200
+    cols = [int(np.nonzero((outs["wide"][0].numpy() == w[:, None, :]).all(axis=(0, 2)))[0][0]) for w in wide.transpose(1, 0, 2)]
+    assert cols == sorted(set(cols))
+    assert f64.dtype == np.float64 and f64.shape[0] == 7 and f64.shape[1] < 300
+    for n in ("small", "wide", "f64"):
+        assert np.array_equal(np.load(paths[0] / (n + ".npy")), np.load(paths[1] / (n + ".npy")))

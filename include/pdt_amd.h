@@ -338,42 +338,12 @@ int pdt_beam_search_table_paths(const uint32_t *trie, const int32_t *finish, int
                                 int64_t width, int64_t T, int64_t pad_value, int64_t *y, void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * One frame of CTCPrefixSearch with a LookupLanguageModel in the loop as one kernel
- * (_decoding.py:1110-1163 around :636-934; scores: _lm.py:403-515): the back-off n-gram scores of
- * every prefix's context (its last max_ngram - 1 tokens, read from y_prev), shallow fusion
- * (valid_mixture = 0: ext = p_ctc * exp(beta * log_softmax(lm))) or the valid mixture, the
- * per-prefix sorted lists and the prefix step.  State arguments and outputs are those of
- * pdt_ctc_prefix_search_advance (without ext); the model's buffers are those of
- * pdt_lookup_lm_log_probs (the forward index is required); max_ngram >= 2.
- * history_bytes: 8 -- y_prev / y_next hold int64 tokens, as the step functions exchange them; 2 --
- * int16 tokens (V <= 32767): a caller that runs frame after frame keeps the (t, N, K) history in
- * this narrow form between its frames (copying it is what a long search pays per frame).
- * yn_ss / yn_sn / yn_sk: element strides of y_next, rows 0 .. S written ((S + 1, N, width) contiguous is
- * N * width, width, 1; a frame loop that keeps token-contiguous (N, width, Smax) int16 histories --
- * strides 1, width * Smax, Smax, Smax a multiple of 8 -- has them copied 16 bytes at a time).
- * frame_lens (N,) int64 or NULL, frame: a batch element with frame_lens[n] <= frame has no such frame
- * and keeps its beam -- y / lens / nb / b as they were (brought to `width`), one more row of zeros
- * (_decoding.py:1165-1181); its last tokens and is-prefix outputs are unspecified.
- * width, Kp <= 32; max_ngram <= 16.  Same bits as pdt_lookup_lm_log_probs -> pdt_fusion_ext ->
- * pdt_ctc_prefix_search_advance.
- * ------------------------------------------------------------------------------------- */
-int pdt_ctc_lookup_lm_advance(
-    const float *nonext, int64_t ne_sn, int64_t ne_sv, const float *blank, int64_t bl_sn, int64_t N, int64_t Kp,
-    int64_t V, int64_t width, const float *nb_prev, int64_t nb_sn, int64_t nb_sk, const float *b_prev,
-    int64_t b_sn, int64_t b_sk, const void *y_prev, int64_t S, int64_t yp_ss, int64_t yp_sn, int64_t yp_sk,
-    const int64_t *y_prev_last, int64_t la_sn, int64_t la_sk, const int64_t *y_prev_lens, int64_t le_sn,
-    int64_t le_sk, const uint8_t *prev_is_prefix, int64_t ip_sn, int64_t ip_sa, int64_t ip_sb,
-    const float *logps, const float *logbs, const int32_t *child_start, const int32_t *ids,
-    const int32_t *succ_start, const int32_t *succ_tok, const int32_t *succ_node, int64_t max_ngram, int64_t U,
-    int64_t sos, float beta, int valid_mixture, void *y_next, int64_t *y_next_last, int64_t *y_next_lens,
-    float *nb_next, float *b_next, uint8_t *next_is_prefix, int64_t *next_src, uint8_t *next_is_nonext,
-    int history_bytes, const int64_t *frame_lens, int64_t frame, int64_t yn_ss, int64_t yn_sn, int64_t yn_sk,
-    void *stream);
-
-/* ---------------------------------------------------------------------------------------
  * The whole CTCPrefixSearch with a LookupLanguageModel in the loop (_decoding.py:1083-1202 with
- * :1110-1163 per frame): the frame kernel of pdt_ctc_lookup_lm_advance launched n_frames times
- * from this call, the beam's state kept in `workspace` between the frames.
+ * :1110-1163 per frame; scores: _lm.py:403-515), every frame in one launch, the beam's state kept in
+ * `workspace` between the frames.  A frame: the back-off n-gram scores of every prefix's context (its
+ * last max_ngram - 1 tokens), shallow fusion (valid_mixture = 0: ext = p_ctc * exp(beta *
+ * log_softmax(lm))) or the valid mixture, the per-prefix sorted lists and the prefix step.  The
+ * model's buffers are those of pdt_lookup_lm_log_probs (the forward index is required); max_ngram >= 2.
  *   probs (T, N, V + 1) float32 through element strides: softmax of the logits, blank last; frames
  *   0 .. n_frames - 1 are read (n_frames >= 1).  frame_lens (N,) int64 or NULL: a batch element keeps
  *   its beam from frame frame_lens[n] on (:1165-1181).
@@ -382,9 +352,8 @@ int pdt_ctc_lookup_lm_advance(
  *   source's tokens and the new token (int16 tokens when V <= 32767, int64 otherwise).
  *   Outputs, contiguous: y (n_frames, N, width) int64, zero beyond an entry's length and for absent
  *   entries; y_lens (N, width) int64; nb, b (N, width) float32 -- the two masses of every entry (the
- *   module returns nb + b).  Same bits as n_frames calls of pdt_ctc_lookup_lm_advance.
- *   The model's factor of the mix depends on the context only; for a bigram model whose table of
- *   U rows of V floats stays below 1 GiB the workspace keeps every row once it has been computed.
+ *   module returns nb + b).  Same bits as pdt_lookup_lm_log_probs -> pdt_fusion_ext ->
+ *   pdt_ctc_prefix_search_advance frame after frame.
  *   workspace: pdt_ctc_lookup_lm_search_workspace_bytes(n_frames, N, V, width, max_ngram, U) bytes.
  * width <= 32; max_ngram <= 16.
  * ------------------------------------------------------------------------------------- */

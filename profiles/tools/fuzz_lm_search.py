@@ -1,6 +1,6 @@
-"""One-off fuzz of pdt_ctc_lookup_lm_search (the whole search from one call: history slots, cached
-factor rows) against the host's frame loop around the one-kernel frames and, every fourth case, the
-three-kernel route: random models of order 2-4, widths, vocabularies, ragged lengths, both mixes."""
+"""One-off fuzz of pdt_ctc_lookup_lm_search (the whole search from one call: history slots) against the
+host's frame loop through the model's scores and the step kernel (PDT_CTC_LM_FUSED=0): random models of
+order 2-4, widths, vocabularies, ragged lengths, both mixes."""
 import os, sys, numpy as np, torch
 sys.path.insert(0, "."); sys.path.insert(0, "pydrobert-pytorch_amd"); sys.path.insert(0, "tests")
 from pydrobert_amd import modules as M
@@ -26,10 +26,9 @@ for it in range(cases):
     lens = torch.from_numpy(rng.integers(0, T + 1, N)).to(dev) if rng.random() < 0.6 else None
     search = M.CTCPrefixSearch(W, beta, lm, valid_mixture=vm)
     x = torch.from_numpy(lg).to(dev)
-    switches.set("PDT_CTC_LM_FUSED", 1); switches.set("PDT_CTC_LM_SEARCH", 1)
+    switches.set("PDT_CTC_LM_FUSED", 1)
     y, yl, yp = search(x, lens)
-    switches.set("PDT_CTC_LM_SEARCH", 0)
-    if it % 4 == 3: switches.set("PDT_CTC_LM_FUSED", 0)
+    switches.set("PDT_CTC_LM_FUSED", 0)
     ey, eyl, eyp = search(x, lens)
     mask = torch.arange(y.shape[0], device=dev).view(-1, 1, 1) < yl.unsqueeze(0)
     ok = y.shape == ey.shape and torch.equal(yl, eyl) and torch.equal(yp, eyp) and torch.equal(torch.where(mask, y, ey), ey)

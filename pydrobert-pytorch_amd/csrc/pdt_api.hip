@@ -63,13 +63,10 @@ struct SwitchName {
   int deft;
 };
 const SwitchName kSwitchNames[] = {
-    {"PDT_LEV_BITPAR", &Switches::lev_bitpar, 1},       {"PDT_OC_BITPAR", &Switches::oc_bitpar, 1},
-    {"PDT_OC_WAVES", &Switches::oc_waves, 0},           {"PDT_CTC_EXACT_DIV", &Switches::ctc_exact_div, 0},
-    {"PDT_CTC_ROWREG", &Switches::ctc_rowreg, 1},       {"PDT_STEP_WIDE", &Switches::step_wide, 0},
-    {"PDT_LM_CACHE", &Switches::lm_cache, 0},           {"PDT_LM_PERSISTENT", &Switches::lm_persistent, 1},
-    {"PDT_LM_STEP_WAVES", &Switches::lm_step_waves, 0}, {"PDT_WARP_BANDS", &Switches::warp_bands, 1},
-    {"PDT_CTC_LEAN_EXTRA", &Switches::ctc_lean_extra, 1}, {"PDT_CTC_PAIR", &Switches::ctc_pair, 1},
-    {"PDT_STEP_FLAT", &Switches::step_flat, 1},
+    {"PDT_LEV_BITPAR", &Switches::lev_bitpar, 1},         {"PDT_OC_BITPAR", &Switches::oc_bitpar, 1},
+    {"PDT_CTC_EXACT_DIV", &Switches::ctc_exact_div, 0},   {"PDT_CTC_ROWREG", &Switches::ctc_rowreg, 1},
+    {"PDT_STEP_WIDE", &Switches::step_wide, 0},           {"PDT_CTC_LEAN_EXTRA", &Switches::ctc_lean_extra, 1},
+    {"PDT_CTC_PAIR", &Switches::ctc_pair, 1},             {"PDT_STEP_FLAT", &Switches::step_flat, 1},
 };
 }  // namespace
 
@@ -110,7 +107,11 @@ extern "C" {
 //    pdt_beam_search_step_table, pdt_row_log_softmax_stats
 // 7: pdt_amd_set_switch / pdt_amd_get_switch; the four-utterances-per-wave CTC form left the library
 // 9: pdt_spec_augment_apply_warp; pdt_ctc_lm_table_search takes ctx_base / ctx_mod; PDT_E_UNSUPPORTED
-int pdt_amd_abi_version(void) { return 10; }
+// 10: pdt_ctc_prefix_search_advance_lm; pdt_beam_search_table, pdt_beam_search_table_paths; pdt_lens_reach
+// 11: the one-frame entry point of the n-gram CTC search left the library (pdt_ctc_lookup_lm_search
+//     runs every frame), and with it five switches of comparison-only routes; the search's workspace
+//     keeps no factor rows
+int pdt_amd_abi_version(void) { return 11; }
 
 int pdt_amd_set_switch(const char *name, int value) {
   if (!name) return PDT_E_ARG;

@@ -14,6 +14,9 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd.so"))
 
+# what pdt_amd_abi_version() must report: the table below is this version's
+ABI_VERSION = 11
+
 PDT_OK = 0
 PDT_E_ARG = -1
 PDT_E_TOO_LONG = -2
@@ -80,12 +83,6 @@ SIGNATURES = {
         _INT,
         [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64]
         + [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P],
-    ),
-    "pdt_ctc_lookup_lm_advance": (
-        _INT,
-        [_P, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64]
-        + [_P, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I64]
-        + [_F, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _INT, _P, _I64, _I64, _I64, _I64, _P],
     ),
     "pdt_ctc_lookup_lm_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64]),
     "pdt_ctc_lookup_lm_search": (
@@ -182,7 +179,8 @@ _lib = None
 
 
 def lib():
-    """Load (once) and return the native library; raises if it is not built."""
+    """Load (once) and return the native library; raises if it is not built or was built for
+    another ABI version (a stale library must not be called through a changed table)."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
@@ -193,6 +191,14 @@ def lib():
                 "implementation.".format(LIB_PATH)
             )
         L = ctypes.CDLL(LIB_PATH)
+        L.pdt_amd_abi_version.restype = _INT
+        L.pdt_amd_abi_version.argtypes = []
+        version = L.pdt_amd_abi_version()
+        if version != ABI_VERSION:
+            raise ImportError(
+                "pydrobert_amd: native library {} has ABI version {}, this package expects {}. "
+                "Rebuild it (`make -C pydrobert-pytorch_amd/csrc`).".format(LIB_PATH, version, ABI_VERSION)
+            )
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)
             fn.restype = res
@@ -209,6 +215,8 @@ def check(rc, what):
         raise RuntimeError("{}: invalid argument".format(what))
     if rc == PDT_E_TOO_LONG:
         raise RuntimeError("{}: sequence too long for the MI355X kernel".format(what))
+    if rc == PDT_E_UNSUPPORTED:
+        raise RuntimeError("{}: no kernel for this layout".format(what))
     raise RuntimeError("{}: HIP error {}".format(what, rc))
 
 

@@ -9,7 +9,7 @@ user-supplied language model.
 """
 import math
 import weakref
-from typing import Any, Dict, List, Optional, Tuple
+from typing import Any, Dict, Optional, Tuple
 
 import torch
 from torch.library import custom_op, register_autograd
@@ -628,13 +628,6 @@ def _fusion_ext_op(
     return _fusion_ext_impl(lm_log_probs, nonext, blank, beta, valid_mixture)
 
 
-def _fusion_ext(lm_log_probs, nonext, blank, beta, valid_mixture):
-    """The operator, or -- nothing tracing, transforming or differentiating -- what is behind it."""
-    if _cabi.plain_call(lm_log_probs, nonext, blank):
-        return _fusion_ext_impl(lm_log_probs, nonext, blank, beta, valid_mixture)
-    return torch.ops.pydrobert_amd.fusion_ext(lm_log_probs, nonext, blank, beta, valid_mixture)
-
-
 @_fusion_ext_op.register_fake
 def _(lm_log_probs, nonext, blank, beta, valid_mixture):
     N, V = nonext.shape
@@ -715,14 +708,17 @@ class CTCPrefixSearch(torch.nn.Module):
 
     @torch.jit.unused
     def _fuses_lookup_lm(self, logits: torch.Tensor) -> bool:
-        """Whether a frame with the language model in the loop can run as ONE kernel
-        (csrc/ctc_lm_step.hip): the model is this package's n-gram LookupLanguageModel with its own
-        scoring methods (a subclass that overrides them must be called), of order two or more with its
-        forward index built, the beam fits the frame routine and nothing wants gradients."""
+        """Whether the search with the language model in the loop can run from one call of the library
+        (csrc/ctc_lm_step.hip, csrc/ctc_lm_table.hip): the model is this package's n-gram
+        LookupLanguageModel with its own scoring methods (a subclass that overrides them must be called),
+        of order two or more with its forward index built, the beam fits the frame routine, the logits
+        are float32 and nothing wants gradients."""
         lm = self.lm
         if type(lm) is not LookupLanguageModel or not switches.get("PDT_CTC_LM_FUSED"):
             return False
         if lm.max_ngram < 2 or self.width > 32 or self.beta == 0.0 or logits.device.type != "cuda":
+            return False
+        if logits.dtype != torch.float:
             return False
         shift = 0 if (0 <= lm.sos < lm.vocab_size) else 1
         if lm.succ_start.numel() != lm.vocab_size + shift + 2 or lm.logps.device != logits.device:
@@ -730,59 +726,12 @@ class CTCPrefixSearch(torch.nn.Module):
         return not (torch.is_grad_enabled() and logits.requires_grad)
 
     @torch.jit.unused
-    def _lookup_lm_frame(
-        self, nonext: torch.Tensor, blank: torch.Tensor, nb: torch.Tensor, b: torch.Tensor, y: torch.Tensor,
-        y_last: torch.Tensor, y_lens: torch.Tensor, is_prefix: torch.Tensor, y_next: torch.Tensor,
-        lens: Optional[torch.Tensor], t: int,
-    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-        """Scores of the n-gram model, the mix with the frame's probabilities and the prefix step in one
-        launch (include/pdt_amd.h: pdt_ctc_lookup_lm_advance).  ``y_next`` (t + 1, N, W) is written in
-        place (the caller alternates between two buffers); utterances with ``lens <= t`` keep their beam."""
-        lm, W = self.lm, self.width
-        N, V = nonext.shape
-        Kp, S = nb.size(1), y.size(0)
-        device = _cabi.require_hip(nonext, blank, nb, b, y, y_last, y_lens, is_prefix, y_next, lens, *_lm_buffers(lm))
-        nonext, blank, nb, b = (_f32(x) for x in (nonext, blank, nb, b))
-        shift = 0 if (0 <= lm.sos < V) else 1
-        with torch.cuda.device(device):
-            o_last = torch.empty((N, W), device=device, dtype=torch.long)
-            o_lens = torch.empty((N, W), device=device, dtype=torch.long)
-            o_src = torch.empty((N, W), device=device, dtype=torch.long)
-            o_nb = torch.empty((N, W), device=device, dtype=torch.float)
-            o_b = torch.empty((N, W), device=device, dtype=torch.float)
-            o_isp = torch.empty((N, W, W), device=device, dtype=torch.bool)
-            o_non = torch.empty((N, W), device=device, dtype=torch.bool)
-            if N:
-                rc = _cabi.lib().pdt_ctc_lookup_lm_advance(
-                    _cabi.ptr(nonext), nonext.stride(0), nonext.stride(1), _cabi.ptr(blank), blank.stride(0),
-                    N, Kp, V, W, _cabi.ptr(nb), nb.stride(0), nb.stride(1), _cabi.ptr(b), b.stride(0), b.stride(1),
-                    _cabi.ptr(y), S, y.stride(0), y.stride(1), y.stride(2),
-                    _cabi.ptr(y_last), y_last.stride(0), y_last.stride(1),
-                    _cabi.ptr(y_lens), y_lens.stride(0), y_lens.stride(1),
-                    _cabi.ptr(is_prefix), is_prefix.stride(0), is_prefix.stride(1), is_prefix.stride(2),
-                    _cabi.ptr(lm.logps), _cabi.ptr(lm.logbs), _cabi.ptr(lm.child_start), _cabi.ptr(lm.ids_wide),
-                    _cabi.ptr(lm.succ_start), _cabi.ptr(lm.succ_tok), _cabi.ptr(lm.succ_node),
-                    lm.max_ngram, V + shift + 1, lm.sos, float(self.beta), int(self.valid_mixture),
-                    _cabi.ptr(y_next), _cabi.ptr(o_last), _cabi.ptr(o_lens), _cabi.ptr(o_nb), _cabi.ptr(o_b),
-                    _cabi.ptr(o_isp), _cabi.ptr(o_src), _cabi.ptr(o_non), y.element_size(),
-                    _cabi.ptr(lens), t, y_next.stride(0), y_next.stride(1), y_next.stride(2),
-                    _cabi.stream_ptr(device),
-                )  # fmt: skip
-                _cabi.check(rc, "pdt_ctc_lookup_lm_advance")
-        return o_last, o_lens, o_nb, o_b, o_isp
-
-    @torch.jit.unused
-    def _searches_in_one_call(self) -> bool:
-        """PDT_CTC_LM_SEARCH=0 keeps the host's frame loop around the one-kernel frames (comparisons)."""
-        return switches.get("PDT_CTC_LM_SEARCH") != 0
-
-    @torch.jit.unused
     def _lookup_lm_search(
         self, probs: torch.Tensor, lens: Optional[torch.Tensor], n_frames: int
     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """Every frame of the search with the n-gram model in the loop from ONE call of the library
-        (include/pdt_amd.h: pdt_ctc_lookup_lm_search): the frame kernel of :meth:`_lookup_lm_frame`
-        launched ``n_frames`` times from C, the beam's state and histories in a workspace in between."""
+        (include/pdt_amd.h: pdt_ctc_lookup_lm_search): every frame in one launch, the beam's state and
+        histories in a workspace in between."""
         lm, W = self.lm, self.width
         T, N, V = probs.size(0), probs.size(1), probs.size(2) - 1
         device = _cabi.require_hip(probs, lens, *_lm_buffers(lm))
@@ -810,17 +759,18 @@ class CTCPrefixSearch(torch.nn.Module):
         return y, y_lens, nb + b
 
     @torch.jit.unused
-    def _searches_through_a_factor_table(self, logits: torch.Tensor) -> bool:
-        """A bigram LookupLanguageModel whose (contexts, V) factor table stays in the Infinity Cache:
-        the search of csrc/ctc_lm_table.hip (PDT_CTC_LM_TABLE=0: the other routes, for comparisons)."""
+    def _searches_through_a_factor_table(self) -> bool:
+        """Of the searches :meth:`_fuses_lookup_lm` admits, those whose (contexts, V) factor table is
+        small enough: the search of csrc/ctc_lm_table.hip (PDT_CTC_LM_TABLE=0: the one of
+        csrc/ctc_lm_step.hip, for comparisons)."""
         lm = self.lm
-        if not switches.get("PDT_CTC_LM_TABLE") or not self._fuses_lookup_lm(logits) or lm.max_ngram < 2:
+        if not switches.get("PDT_CTC_LM_TABLE"):
             return False
         V = lm.vocab_size
         # (a row per context: U^(order - 1) of them -- 4 MB for a bigram model over 1000 tokens, 4 GB for a
         # trigram model: the card has 288)
         rows = (V + 1) ** (lm.max_ngram - 1)
-        return V + 1 <= 80 * 64 and rows < (1 << 30) and rows * V * 4 <= _FACTOR_TABLE_MAX_BYTES and logits.dtype == torch.float
+        return V + 1 <= 80 * 64 and rows < (1 << 30) and rows * V * 4 <= _FACTOR_TABLE_MAX_BYTES
 
     @torch.jit.unused
     def _lm_table_search(
@@ -869,8 +819,11 @@ class CTCPrefixSearch(torch.nn.Module):
                 raise RuntimeError("expected dim 0 of lens to be {}, got {}".format(N, lens.size(0)))
             n_frames = min(T, int(lens.max().item())) if N else 0
         if not torch.jit.is_scripting():
-            if self.lm is not None and self.beta != 0.0 and n_frames > 0 and self._searches_through_a_factor_table(logits):
-                return self._lm_table_search(logits, lens, n_frames)
+            # this package's n-gram model in the loop: the whole search from one call of the library
+            if self.lm is not None and self.beta != 0.0 and n_frames > 0 and self._fuses_lookup_lm(logits):
+                if self._searches_through_a_factor_table():
+                    return self._lm_table_search(logits, lens, n_frames)
+                return self._lookup_lm_search(logits.softmax(2), lens, n_frames)
         probs = logits.softmax(2)
         # beam state: one empty prefix per utterance, all of its mass on "ends in blank"
         nb = torch.zeros((N, 1), device=device, dtype=dtype)
@@ -880,27 +833,8 @@ class CTCPrefixSearch(torch.nn.Module):
         y_last = y_lens
         is_prefix = torch.ones((N, 1, 1), device=device, dtype=torch.bool)
         fuse = self.beta != 0.0
-        one_kernel = False  # the n-gram model scored inside the step kernel (csrc/ctc_lm_step.hip)
-        hist_pair: List[torch.Tensor] = []
-        lens_dev: Optional[torch.Tensor] = None
-        if self.lm is not None:
-            if fuse:
-                if not torch.jit.is_scripting():
-                    one_kernel = self._fuses_lookup_lm(logits) and dtype == torch.float
-                if one_kernel and n_frames > 0:
-                    if self._searches_in_one_call():
-                        return self._lookup_lm_search(probs, lens, n_frames)
-                state = self.lm.update_input(state, y)
-                if one_kernel:
-                    # the history as 16-bit tokens between the frames (copying the (t, N, K) tensor is what a
-                    # long search pays per frame), in two buffers of the final size used in turn
-                    # ... each history token-contiguous -- (N, W, S) storage seen as (S, N, W) -- so that a
-                    # column of the new beam is a plain 16-byte-at-a-time copy of its source's
-                    y = y.to(torch.int16 if V <= 32767 else torch.long)
-                    s_max = (n_frames + 7) // 8 * 8
-                    hist_pair = [torch.empty((N, W, s_max), dtype=y.dtype, device=device).permute(2, 0, 1)
-                                 for _ in range(2)]
-                    lens_dev = None if lens is None else _i64(lens).contiguous()
+        if self.lm is not None and fuse:
+            state = self.lm.update_input(state, y)
         Kp = 1
         # row of batch element n's first prefix in the flattened (N * K') LM state, before and after
         # the beam has its full width
@@ -912,15 +846,6 @@ class CTCPrefixSearch(torch.nn.Module):
             state_next: Dict[str, torch.Tensor] = dict()
             mix_in_step = False
             lm_lp = nonext_t
-            if one_kernel:
-                # (the model keeps no state between frames: nothing to extract or mix afterwards; the
-                # history alternates between two buffers of the final size: no allocation per frame)
-                y_new = hist_pair[t % 2][: t + 1]
-                y_last, y_lens, nb, b, is_prefix = self._lookup_lm_frame(
-                    nonext_t, blank_t, nb, b, y, y_last, y_lens, is_prefix, y_new, lens_dev, t
-                )
-                y, Kp = y_new, W
-                continue
             if self.lm is not None:
                 if fuse:
                     lm_lp, state_next = self.lm.calc_idx_log_probs(y.flatten(1), state, y_lens.flatten())
@@ -931,12 +856,8 @@ class CTCPrefixSearch(torch.nn.Module):
                             ext_t = torch.ops.pydrobert_amd.fusion_ext(
                                 lm_lp.reshape(N * Kp, V), nonext_t, blank_t, self.beta, self.valid_mixture
                             )
-                        elif switches.get("PDT_CTC_STEP_MIX"):
-                            mix_in_step = True
                         else:
-                            ext_t = _fusion_ext(
-                                lm_lp.reshape(N * Kp, V), nonext_t, blank_t, self.beta, self.valid_mixture
-                            )
+                            mix_in_step = True
                     elif self.valid_mixture:  # convex combination that still sums to 1 - blank (:1120-1128)
                         lm_p = lm_lp.softmax(-1).view(N, Kp, V) * (1 - blank_t.view(N, 1, 1))
                         ext_t = (1.0 - self.beta) * ext_t + self.beta * lm_p
@@ -975,8 +896,7 @@ class CTCPrefixSearch(torch.nn.Module):
                 lens_new = torch.where(live, lens_new, y_lens)
                 nb_new, b_new = torch.where(live, nb_new, nb), torch.where(live, b_new, b)
             y, y_last, y_lens, nb, b, Kp = y_new, last_new, lens_new, nb_new, b_new, W
-        if y.dtype != torch.long or not y.is_contiguous():
-            y = y.long().contiguous()
+        y = y.contiguous()
         total = nb + b
         if Kp < W:  # no frame at all: fill the beam with absent entries (:1190-1200)
             y, y_lens = y.repeat(1, 1, W), y_lens.repeat(1, W)

@@ -19,10 +19,8 @@ _HOST_DEFAULTS = {
     # (ref, hyp) pair.  OFF by default: a hit is decided by tensor identity, which in-place writes
     # that bypass the version counter (`.data`, raw pointers, graph replays) do not change.
     "PDT_LEV_CACHE": 0,
-    "PDT_CTC_LM_FUSED": 1,  # CTCPrefixSearch + LookupLanguageModel: a frame in one kernel
-    "PDT_CTC_LM_SEARCH": 1,  # ... and every frame from one call of the library
+    "PDT_CTC_LM_FUSED": 1,  # CTCPrefixSearch + LookupLanguageModel: every frame from one call of the library (0: the host's frame loop)
     "PDT_CTC_LM_TABLE": 1,  # ... a bigram model's factor rows from a table built once per model (csrc/ctc_lm_table.hip)
-    "PDT_CTC_STEP_MIX": 1,  # CTCPrefixSearch + any other LM: the step kernel forms the extension probabilities itself (0: fusion_ext first)
     "PDT_BEAM_FUSED": 1,  # BeamSearch: one kernel per iteration
     "PDT_BEAM_SEARCH": 1,  # ... and every iteration from ONE launch, the paths read off a trie at the end (csrc/beam_step.hip)
     "PDT_BEAM_TABLE": 1,  # BeamSearch over a bigram LookupLanguageModel reads its dense table
@@ -30,9 +28,8 @@ _HOST_DEFAULTS = {
 }
 # switches of the native library (csrc/switches.hpp); the library reads the environment itself
 _NATIVE = (
-    "PDT_LEV_BITPAR", "PDT_OC_BITPAR", "PDT_OC_WAVES", "PDT_CTC_EXACT_DIV", "PDT_CTC_ROWREG",
-    "PDT_STEP_WIDE", "PDT_LM_CACHE", "PDT_LM_PERSISTENT", "PDT_LM_STEP_WAVES", "PDT_WARP_BANDS", "PDT_CTC_LEAN_EXTRA",
-    "PDT_CTC_PAIR", "PDT_STEP_FLAT",
+    "PDT_LEV_BITPAR", "PDT_OC_BITPAR", "PDT_CTC_EXACT_DIV", "PDT_CTC_ROWREG", "PDT_STEP_WIDE",
+    "PDT_CTC_LEAN_EXTRA", "PDT_CTC_PAIR", "PDT_STEP_FLAT",
 )  # fmt: skip
 
 

@@ -61,7 +61,7 @@ def test_abi_version_and_arg_validation_without_gpu(lib):
     so these calls are safe on a machine without a GPU."""
     from pydrobert_amd import _cabi
 
-    assert lib.pdt_amd_abi_version() >= 1
+    assert lib.pdt_amd_abi_version() == _cabi.ABI_VERSION
     assert lib.pdt_oc_mask_words(512) == 16 and lib.pdt_oc_mask_words(513) == 17
     assert lib.pdt_ctc_prefix_search_workspace_bytes(10, 4, 30, 16) >= 10 * 4 * 16 * 8
     assert lib.pdt_spline_workspace_bytes(2, 3, 1, 1) > 0
@@ -100,6 +100,8 @@ def test_check_maps_status_to_runtime_error():
     for rc in (_cabi.PDT_E_ARG, _cabi.PDT_E_TOO_LONG, 700):
         with pytest.raises(RuntimeError):
             _cabi.check(rc, "x")
+    with pytest.raises(RuntimeError, match="no kernel for this layout"):
+        _cabi.check(_cabi.PDT_E_UNSUPPORTED, "x")
 
 
 def test_switches_read_once_and_settable(lib):

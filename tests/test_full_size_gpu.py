@@ -229,7 +229,8 @@ def test_c3_searches_with_the_bigram_model_in_the_loop(device, switch):
     slots, factor rows scored in the kernel): the same prefixes and lengths, probabilities to 1e-5 on
     the logarithm, except where two masses of a beam sit within 1e-5 of each other (the two softmaxes
     differ in the last ulp) -- at most a handful of utterances in 1024.  That second route equals the
-    host's frame loop around the same frame kernel to the bit -- ragged lengths, both mixes -- and
+    host's frame loop through the model's scores and the step kernel (PDT_CTC_LM_FUSED=0) to the bit --
+    ragged lengths, both mixes -- and
     BeamSearch reading the model's dense table equals BeamSearch with the model scoring every prefix."""
     import bench
     from pydrobert_amd import modules as M
@@ -245,10 +246,10 @@ def test_c3_searches_with_the_bigram_model_in_the_loop(device, switch):
             switch("PDT_CTC_LM_TABLE", "1")
             ty, tyl, typ = search(lg, ln)
             switch("PDT_CTC_LM_TABLE", "0")
-            switch("PDT_CTC_LM_SEARCH", "1")
             y, yl, yp = search(lg, ln)
-            switch("PDT_CTC_LM_SEARCH", "0")
+            switch("PDT_CTC_LM_FUSED", "0")
             ey, eyl, eyp = search(lg, ln)
+            switch("PDT_CTC_LM_FUSED", "1")
             mask = torch.arange(y.shape[0], device=device).view(-1, 1, 1) < yl.unsqueeze(0)
             assert torch.equal(yl, eyl) and torch.equal(yp, eyp) and torch.equal(torch.where(mask, y, ey), ey), vm
             assert bool((yp > 0).all()) and bool((typ > 0).all())

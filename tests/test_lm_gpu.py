@@ -141,11 +141,11 @@ def test_ctc_prefix_search_with_lookup_lm_fusion():
 
 @pytest.mark.parametrize("order", [2, 3, 4])
 def test_one_kernel_frames_equal_the_three_kernel_route(order, switch):
-    """A frame of CTCPrefixSearch with the n-gram model in the loop as ONE kernel
-    (csrc/ctc_lm_step.hip: scores, mix, lists, prefix step) against the route through
-    lookup_lm_log_probs -> fusion_ext -> ctc_prefix_search_advance (PDT_CTC_LM_FUSED=0): the same
-    arithmetic in the same order, so the same bits -- shallow fusion and valid mixture, ragged lens,
-    sos in and outside the vocabulary, widths below and above the number of tokens."""
+    """CTCPrefixSearch with the n-gram model in the loop, every frame in ONE launch
+    (csrc/ctc_lm_step.hip: scores, mix, lists, prefix step per frame) against the host's frame loop
+    through lookup_lm_log_probs and the step kernel (PDT_CTC_LM_FUSED=0): the same arithmetic in the
+    same order, so the same bits -- shallow fusion and valid mixture, ragged lens, sos in and outside
+    the vocabulary, widths below and above the number of tokens."""
     rng = np.random.default_rng(700 + order)
     big = 40 if order == 2 else 12
     for V, W, T, N, sos, vm, beta in [(9, 4, 14, 5, -1, False, 0.3), (6, 8, 9, 3, 2, True, 0.6),
@@ -164,16 +164,14 @@ def test_one_kernel_frames_equal_the_three_kernel_route(order, switch):
             ey, eyl, eyp = search(_t(lg), ln)
             switch("PDT_CTC_LM_FUSED", "1")
             assert search._fuses_lookup_lm(_t(lg))
-            # one kernel per frame launched by the host loop, then every frame from one call of the
-            # library (histories in slots instead of copied from frame to frame)
-            for whole in ("0", "1"):
-                switch("PDT_CTC_LM_SEARCH", whole)
-                y, yl, yp = search(_t(lg), ln)
-                what = (order, V, W, vm, ln is None, whole)
-                assert torch.isfinite(eyp[:, 0]).all(), what
-                assert y.shape == ey.shape and torch.equal(yl, eyl) and torch.equal(yp, eyp), what
-                mask = torch.arange(y.shape[0], device=DEV).view(-1, 1, 1) < yl.unsqueeze(0)
-                assert torch.equal(torch.where(mask, y, ey), ey), what
+            # every frame from one call of the library (histories in slots instead of copied from
+            # frame to frame)
+            y, yl, yp = search(_t(lg), ln)
+            what = (order, V, W, vm, ln is None)
+            assert torch.isfinite(eyp[:, 0]).all(), what
+            assert y.shape == ey.shape and torch.equal(yl, eyl) and torch.equal(yp, eyp), what
+            mask = torch.arange(y.shape[0], device=DEV).view(-1, 1, 1) < yl.unsqueeze(0)
+            assert torch.equal(torch.where(mask, y, ey), ey), what
 
 
 def test_beam_search_with_lookup_lm():

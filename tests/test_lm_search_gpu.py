@@ -7,9 +7,9 @@ mistake shared by the host loop and the fused kernels cannot pass: neither is th
 
 Routes of CTCPrefixSearch + LookupLanguageModel: "table" = the whole search in one launch with a
 bigram model's factor rows read from a table (pdt_ctc_lm_table_search; the default for order two --
-higher orders take "search"), "search" = every frame from one library call
-(pdt_ctc_lookup_lm_search), "frame" = the host's loop around the one-kernel frame
-(pdt_ctc_lookup_lm_advance), "three" = lookup scores -> fusion_ext -> ctc_prefix_search_advance.
+higher orders take "search"), "search" = every frame in one launch from one library call
+(pdt_ctc_lookup_lm_search), "three" = the host's frame loop: lookup scores -> the step kernel that
+mixes them in (ctc_prefix_search_advance with the model's scores).
 Routes of BeamSearch: "table" = fused iterations reading a bigram model's dense table, "fused" = fused
 iterations around the model's forward, "loop" = the reference-shaped loop around beam_search_advance."""
 import numpy as np
@@ -25,9 +25,8 @@ from _toy_lm import CounterLM
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-CTC_ROUTES = {"table": dict(PDT_CTC_LM_TABLE=1, PDT_CTC_LM_FUSED=1, PDT_CTC_LM_SEARCH=1),
-              "search": dict(PDT_CTC_LM_TABLE=0, PDT_CTC_LM_FUSED=1, PDT_CTC_LM_SEARCH=1),
-              "frame": dict(PDT_CTC_LM_TABLE=0, PDT_CTC_LM_FUSED=1, PDT_CTC_LM_SEARCH=0),
+CTC_ROUTES = {"table": dict(PDT_CTC_LM_TABLE=1, PDT_CTC_LM_FUSED=1),
+              "search": dict(PDT_CTC_LM_TABLE=0, PDT_CTC_LM_FUSED=1),
               "three": dict(PDT_CTC_LM_TABLE=0, PDT_CTC_LM_FUSED=0)}
 # (search: every iteration of a bigram-table model from ONE launch, the paths read off a trie at the end -- round 5)
 BEAM_ROUTES = {"search": dict(PDT_BEAM_FUSED=1, PDT_BEAM_TABLE=1, PDT_BEAM_SEARCH=1),

@@ -395,6 +395,50 @@ int pdt_row_log_softmax_stats(const float *table, int64_t tb_sr, int64_t tb_sv, 
                               float *stats, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Random walks (reference _decoding.py:1207-1513).  Every token is drawn by one rule from a row x of
+ * log-weights (any normalisation) and a uniform u in [0, 1) the caller draws: with m = max x and
+ * lse = log sum exp(x - m) (as pdt_row_log_softmax_stats forms them), w_v = exp(x_v - m) and Z = exp(lse),
+ * the token is the smallest v with w_v > 0 whose running prefix sum of w exceeds u Z, else the largest v
+ * with w_v > 0.  A row without positive finite mass (all -inf, a NaN, +inf) draws nothing: it raises
+ * PDT_WALK_INVALID and writes token 0.  One wave per walk.
+ * A launch reports through ctl (device int32[4], zeroed before the first launch that uses it; every launch
+ * leaves it zeroed) into host_words (int32[3], pinned host memory): host_words[1] = walks still live,
+ * host_words[2] = the longest walk (table form), and host_words[0] = PDT_WALK_DONE | PDT_WALK_* bits,
+ * stored last with release semantics at system scope -- the host may poll it instead of synchronising.
+ *
+ * pdt_random_walk_advance: random_walk_advance.  log_probs_t (N, V), u / log_probs_prev (N,) float32;
+ *   y_prev (S, N) int64; y_prev_lens (N,) or NULL.  y_next (S + 1, N) contiguous: the history, the token
+ *   in row S and, with lengths and S > 0, in row y_prev_lens[n] (:1272-1279); PDT_WALK_REACH when some
+ *   length reaches S -- the caller keeps S + 1 rows then, or when there are no lengths or S = 0, else S.
+ *   A length outside [0, S] raises PDT_WALK_BAD_LENS and is not written.
+ *   log_probs_next[n] = log_probs_prev[n] + log_probs_t[n, token] (float32; not renormalised).
+ * pdt_random_walk_step: one iteration of RandomWalk.forward with the default hook.  scores (N, V) are the
+ *   model's output; a walk with ended[n] set emits eos at no cost; otherwise it draws from
+ *   log_softmax(scores) with u[n], log_probs[n] += its log-probability, lens[n] += 1, ended[n] = (token ==
+ *   eos).  The token goes to y_t[n].  host_words[1]: walks not ended afterwards.
+ * pdt_random_walk_table: C iterations of the same walk over a dense context table (R, V) of an n-gram
+ *   model and its row_stats (R, 2): walk n continues from context row ctx[n], moving to
+ *   (ctx * U + token) mod R after each token; u (C, N), y (C, N) contiguous; the state (ctx, lens, ended,
+ *   log_probs) is read at the start and written back at the end.
+ * ------------------------------------------------------------------------------------- */
+#define PDT_WALK_DONE 1
+#define PDT_WALK_INVALID 2
+#define PDT_WALK_REACH 4
+#define PDT_WALK_BAD_LENS 8
+int pdt_random_walk_advance(const float *log_probs_t, int64_t lt_sn, int64_t lt_sv, int64_t N, int64_t V,
+                            const float *u, int64_t u_sn, const float *log_probs_prev, int64_t lp_sn,
+                            const int64_t *y_prev, int64_t S, int64_t yp_ss, int64_t yp_sn,
+                            const int64_t *y_prev_lens, int64_t le_sn, int64_t *y_next, float *log_probs_next,
+                            int32_t *ctl, int32_t *host_words, void *stream);
+int pdt_random_walk_step(const float *scores, int64_t sc_sn, int64_t sc_sv, int64_t N, int64_t V, const float *u,
+                         int has_eos, int64_t eos, int64_t *y_t, int64_t *lens, uint8_t *ended, float *log_probs,
+                         int32_t *ctl, int32_t *host_words, void *stream);
+int pdt_random_walk_table(const float *table, int64_t tb_sr, int64_t R, int64_t U, int64_t V, const float *row_stats,
+                          const float *u, int64_t N, int64_t C, int has_eos, int64_t eos, int64_t *y, int64_t *ctx,
+                          int64_t *lens, uint8_t *ended, float *log_probs, int32_t *ctl, int32_t *host_words,
+                          void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * ctc_greedy_search (reference _decoding.py:507-558).  logits (T, N, V) through element
  * strides; blank_idx already normalised to [0, V).  max_out (N,): sum of the per-frame maximum
  * log-probabilities (is_probs: product of the maxima, no normalisation) over frames below

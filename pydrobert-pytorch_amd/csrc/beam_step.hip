@@ -18,6 +18,7 @@
 // One workgroup per batch element, as beam_advance_kernel: the waves take the prefixes' selections
 // in turn, wave 0 merges, all waves copy the history.  Ties: lowest flat index k * V + v.
 #include "ctc_frame.hpp"
+#include "row_sample.hpp"
 #include "switches.hpp"
 
 namespace pdt {
@@ -41,36 +42,6 @@ struct BeamStepArgs {
   const int64_t *rows;
   const float *row_stats;
 };
-
-// maximum and log-sum-exp of a strided row (two passes, eight loads in flight)
-__device__ __forceinline__ void row_log_softmax_stats(const float *x, const int64_t sx, const int V, float &mx_out,
-                                                      float &lse_out) {
-  const int lane = lane_id();
-  float mx = -PDT_INF;
-  int v = lane;
-  for (; v + 7 * PDT_WAVE < V; v += 8 * PDT_WAVE) {
-    float t[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = x[(int64_t)(v + i * PDT_WAVE) * sx];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) mx = fmaxf(mx, t[i]);
-  }
-  for (; v < V; v += PDT_WAVE) mx = fmaxf(mx, x[(int64_t)v * sx]);
-  mx = wave_max_f(mx);
-  float s = 0.0f;
-  v = lane;
-  for (; v + 7 * PDT_WAVE < V; v += 8 * PDT_WAVE) {
-    float t[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) t[i] = x[(int64_t)(v + i * PDT_WAVE) * sx];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += expf(t[i] - mx);
-  }
-  for (; v < V; v += PDT_WAVE) s += expf(x[(int64_t)v * sx] - mx);
-  s = wave_sum_f(s);
-  mx_out = mx;
-  lse_out = logf(s);
-}
 
 __global__ void __launch_bounds__(512) beam_step_kernel(const BeamStepArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];

@@ -67,6 +67,7 @@ const SwitchName kSwitchNames[] = {
     {"PDT_CTC_EXACT_DIV", &Switches::ctc_exact_div, 0},   {"PDT_CTC_ROWREG", &Switches::ctc_rowreg, 1},
     {"PDT_STEP_WIDE", &Switches::step_wide, 0},           {"PDT_CTC_LEAN_EXTRA", &Switches::ctc_lean_extra, 1},
     {"PDT_CTC_PAIR", &Switches::ctc_pair, 1},             {"PDT_STEP_FLAT", &Switches::step_flat, 1},
+    {"PDT_WALK_TABLE", &Switches::walk_table, 1},
 };
 }  // namespace
 
@@ -111,7 +112,8 @@ extern "C" {
 // 11: the one-frame entry point of the n-gram CTC search left the library (pdt_ctc_lookup_lm_search
 //     runs every frame), and with it five switches of comparison-only routes; the search's workspace
 //     keeps no factor rows
-int pdt_amd_abi_version(void) { return 11; }
+// 12: pdt_random_walk_advance, pdt_random_walk_step, pdt_random_walk_table; the switch PDT_WALK_TABLE
+int pdt_amd_abi_version(void) { return 12; }
 
 int pdt_amd_set_switch(const char *name, int value) {
   if (!name) return PDT_E_ARG;

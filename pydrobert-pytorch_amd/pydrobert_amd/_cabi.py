@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd.so"))
 
 # what pdt_amd_abi_version() must report: the table below is this version's
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 PDT_OK = 0
 PDT_E_ARG = -1
@@ -107,6 +107,15 @@ SIGNATURES = {
         + [_P, _I64, _I64, _INT, _I64, _INT, _I64, _P, _P, _P, _P, _P, _P, _P],
     ),
     "pdt_row_log_softmax_stats": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P]),
+    "pdt_random_walk_advance": (
+        _INT,
+        [_P, _I64, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _I64, _I64, _P, _I64, _P, _P, _P, _P, _P],
+    ),
+    "pdt_random_walk_step": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _INT, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "pdt_random_walk_table": (
+        _INT,
+        [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _INT, _I64, _P, _P, _P, _P, _P, _P, _P, _P],
+    ),
     "pdt_ctc_greedy_search": (
         _INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _INT, _P, _P, _I64, _I64, _P, _P],
     ),

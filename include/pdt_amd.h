@@ -653,6 +653,48 @@ int pdt_pad_variable_backward(const float *grad_out, int64_t N, int64_t T, int64
                               const int64_t *lens, const int64_t *pad, int mode, int64_t Tp,
                               float *grad_x, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Feature deltas (reference _feats.py:216-286).  x is indexed (A, B, T, C, D) with element
+ * strides xs_*; dtype 0 float32, 1 float64, 2 float16, 3 bfloat16.  taps (U, 1 + 2P) are in the
+ * compute type (float64 for float64, float32 otherwise); fill is one compute-type element read in
+ * mode 3.  out[u] at position t is sum_k taps[u, k] * xpad[t + k - P] over the padded time axis:
+ * mode 0 replicate, 1 reflect (the caller checks P < T), 2 circular (P <= T), 3 constant.  out
+ * is contiguous (A, U, B, T, C, D), or (A, B, T, C, U, D) when u_inner.  T == 0 is an error.
+ * pdt_feat_deltas_backward: the adjoint, grad_out in the forward's output layout, grad_x
+ * (A, B, T, C, D) contiguous; a gather, deterministic.
+ * ------------------------------------------------------------------------------------- */
+int pdt_feat_deltas(const void *x, int dtype, int64_t A, int64_t B, int64_t T, int64_t C, int64_t D,
+                    int64_t xs_a, int64_t xs_b, int64_t xs_t, int64_t xs_c, int64_t xs_d, const void *taps,
+                    int64_t U, int64_t P, int mode, const void *fill, int u_inner, void *out, void *stream);
+
+int pdt_feat_deltas_backward(const void *grad_out, int dtype, int64_t A, int64_t B, int64_t T, int64_t C,
+                             int64_t D, const void *taps, int64_t U, int64_t P, int mode, int u_inner,
+                             void *grad_x, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Mean/variance normalisation (reference _feats.py:29-214).  x (A, X, B) contiguous, statistics
+ * per index of X over the A * B samples; dtype as for the deltas.
+ * pdt_mvn_stats: a two-stage float64 reduction through a workspace of
+ * pdt_mvn_stats_workspace_bytes(A, X, B) bytes, fixed order, no atomics:
+ *   mode 0  out0 = mean, out1 = population std (sums shifted by the index's first sample)
+ *   mode 1  out0 += sum x, out1 += sum x^2, count[0] += A * B (in place, on the stream)
+ *   mode 2  out0 = sum g, out1 = sum g * c, c = x - mean[i] rounded to x's dtype (g like x)
+ * pdt_mvn_apply: y = (x - mean[i]) / scale[i], mean / scale (X,) in x's dtype, the difference
+ * rounded to x's dtype first.  pdt_mvn_backward: grad_x = grad_y * coef[0, i] + coef[1, i] +
+ * coef[2, i] * c, coef (3, X) in the compute type.
+ * ------------------------------------------------------------------------------------- */
+int64_t pdt_mvn_stats_workspace_bytes(int64_t A, int64_t X, int64_t B);
+
+int pdt_mvn_stats(const void *x, const void *g, const void *mean, int dtype, int64_t A, int64_t X, int64_t B,
+                  int mode, double *out0, double *out1, double *count, void *workspace, int64_t workspace_bytes,
+                  void *stream);
+
+int pdt_mvn_apply(const void *x, int dtype, int64_t A, int64_t X, int64_t B, const void *mean, const void *scale,
+                  void *y, void *stream);
+
+int pdt_mvn_backward(const void *grad_y, const void *x, int dtype, int64_t A, int64_t X, int64_t B, const void *mean,
+                     const void *coef, void *grad_x, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,7 +112,9 @@ extern "C" {
 // 11: the one-frame entry point of the n-gram CTC search left the library (pdt_ctc_lookup_lm_search
 //     runs every frame), and with it five switches of comparison-only routes; the search's workspace
 //     keeps no factor rows
-// 12: pdt_random_walk_advance, pdt_random_walk_step, pdt_random_walk_table; the switch PDT_WALK_TABLE
+// 12: pdt_random_walk_advance, pdt_random_walk_step, pdt_random_walk_table; the switch PDT_WALK_TABLE;
+//     then, additively (no existing entry point changed): pdt_feat_deltas, pdt_feat_deltas_backward,
+//     pdt_mvn_stats_workspace_bytes, pdt_mvn_stats, pdt_mvn_apply, pdt_mvn_backward
 int pdt_amd_abi_version(void) { return 12; }
 
 int pdt_amd_set_switch(const char *name, int value) {

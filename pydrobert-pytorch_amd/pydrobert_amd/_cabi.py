@@ -176,6 +176,16 @@ SIGNATURES = {
     "pdt_fusion_ext": (_INT, [_P, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _F, _INT, _P, _P]),
     "pdt_pad_variable": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P, _INT, _P, _I64, _P, _P]),
     "pdt_pad_variable_backward": (_INT, [_P, _I64, _I64, _I64, _P, _P, _INT, _I64, _P, _P]),
+    "pdt_feat_deltas": (
+        _INT, [_P, _INT, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _INT, _P, _INT, _P, _P],
+    ),
+    "pdt_feat_deltas_backward": (
+        _INT, [_P, _INT, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _INT, _INT, _P, _P],
+    ),
+    "pdt_mvn_stats_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "pdt_mvn_stats": (_INT, [_P, _P, _P, _INT, _I64, _I64, _I64, _INT, _P, _P, _P, _P, _I64, _P]),
+    "pdt_mvn_apply": (_INT, [_P, _INT, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "pdt_mvn_backward": (_INT, [_P, _P, _INT, _I64, _I64, _I64, _P, _P, _P, _P]),
     "pdt_ctc_prefix_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "pdt_ctc_prefix_search_plan": (_INT, [_I64, _I64, _P]),
     "pdt_ctc_prefix_search": (
@@ -209,7 +219,13 @@ def lib():
                 "Rebuild it (`make -C pydrobert-pytorch_amd/csrc`).".format(LIB_PATH, version, ABI_VERSION)
             )
         for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
+            try:
+                fn = getattr(L, name)
+            except AttributeError:  # (a library built before this entry point was added)
+                raise ImportError(
+                    "pydrobert_amd: native library {} lacks {}. Rebuild it "
+                    "(`make -C pydrobert-pytorch_amd/csrc`).".format(LIB_PATH, name)
+                ) from None
             fn.restype = res
             fn.argtypes = args
         _lib = L

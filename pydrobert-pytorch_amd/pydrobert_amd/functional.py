@@ -17,6 +17,7 @@ from ._img import (
     spec_augment_draw_parameters,
     warp_1d_grid,
 )
+from ._feats import feat_deltas, mean_var_norm
 from ._pad import pad_variable
 from ._string import (
     hard_optimal_completion_distillation_loss,
@@ -30,6 +31,8 @@ from ._string import (
 )
 
 __all__ = [
+    "feat_deltas",
+    "mean_var_norm",
     "pad_variable",
     "random_shift",
     "ctc_greedy_search",

@@ -10,6 +10,7 @@ from ._img import (
     SpecAugment,
     Warp1DGrid,
 )
+from ._feats import FeatureDeltas, MeanVarianceNormalization
 from ._pad import PadVariable
 from ._decoding import CTCGreedySearch, RandomWalk, SequenceLogProbabilities
 from ._lm import (
@@ -33,6 +34,8 @@ from ._string import (
 )
 
 __all__ = [
+    "FeatureDeltas",
+    "MeanVarianceNormalization",
     "PadVariable",
     "RandomShift",
     "DenseImageWarp",

@@ -10,10 +10,14 @@ HBM: BASELINE.json's configs[1] shapes (N=4096 utterances per GPU, T=512, V=256)
 `python bench.py --gpus N` starts its own N ranks (one process per GPU, RCCL) when it is not
 already running under torchrun; rank 0 prints ONE JSON line.  `value` = utterances / s over all
 ranks (weak scaling: every rank owns its own N utterances).  Per-op times come from HIP events
-recorded on the launch stream inside the timed region.  After the timed region the line also
-carries the other BASELINE configs (C3 search and step functions, C4 SpecAugment / sparse warp,
-the C5 shard: error_rate + decode at V=5000 with its gather) as `other_configs`, and at N=1 the
-CPU baseline (the reference's tensor algorithm on the host cores, per operator).
+recorded on the launch stream inside the timed region.
+
+A plain run does only what that line needs: set up, warm up, time the steps, write
+--dump-outputs, print.  With --full it also checks the multi-rank gather before timing, and after
+the timed region measures the other BASELINE configs (C3 search and step functions, C4
+SpecAugment / sparse warp, the C5 shard: error_rate + decode at V=5000 with its gather, the
+language-model searches) as `other_configs`, and at N=1 the CPU baseline (the reference's tensor
+algorithm on the host cores, per operator).
 """
 import argparse
 import ctypes
@@ -45,9 +49,11 @@ def parse():
     ap.add_argument("--T", type=int, default=512)
     ap.add_argument("--V", type=int, default=256)
     ap.add_argument("--beam", type=int, default=16)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the multi-rank gather, measure the other configs and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-decode", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configs")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other BASELINE configs")
     ap.add_argument("--cpu-seconds", type=float, default=20.0)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step computed as DIR/<name>.npy (rank 0, e.g. bench_outputs/; "
@@ -822,7 +828,7 @@ def run_rank(args):
 
     for _ in range(args.warmup):
         step()
-    if world > 1:
+    if world > 1 and args.full:
         # once, before timing: the gathered vector is the concatenation of every rank's shard
         # (each rank regenerates every shard's tokens from the rank's seed and scores them itself)
         step()
@@ -917,7 +923,7 @@ def run_rank(args):
         nbytes = dump_outputs(args.dump_outputs, last_outs)
         say("outputs of the last timed step: {} arrays, {} bytes in {}".format(len(last_outs), nbytes, args.dump_outputs))
     extra = None
-    if not args.no_extra and have_decode:
+    if args.full and not args.no_extra and have_decode:
         # (one stderr line per configuration as it finishes, and `config_summary` as the LAST key of the
         #  JSON line: whatever tail of either stream a driver keeps carries every BASELINE config)
         extra = other_configs(F, M, device, world, rank, dist, gather_check, say)
@@ -944,7 +950,7 @@ def run_rank(args):
                 "workload": "BASELINE configs[1] shapes on every GPU (its own N utterances): " + " + ".join(ops),
                 "N_per_gpu": N, "T_ref": T, "T_hyp": T, "V": args.V, "beam": args.beam,
                 "optimal_completion_C": C, "sharding": "batch axis, {} rank(s)".format(world),
-                "gather_verified": world > 1,
+                "gather_verified": world > 1 and args.full,
             },
             "op_ms": op_ms,
             "op_ms_over_ranks": op_ms_ranks,
@@ -969,7 +975,7 @@ def run_rank(args):
         }
         if extra is not None:
             out["other_configs"] = dict(extra)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, have_decode, op_ms)
             say("cpu baseline done")
         if extra is not None:  # LAST key on purpose (see above)

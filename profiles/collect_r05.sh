@@ -1,20 +1,21 @@
 #!/bin/bash
-# Round-5 profiles, on a GPU box (from the repo root through gpurun):
-#   gpurun --timeout 1200 -- 'bash profiles/collect_r05.sh'
-# then, back in the build container:  python profiles/summarize_r05.py gpurun_out
-# Kernel-trace statistics of the bench command (timed step only, and the whole line with every other
+# Round-5 profiles, on a GPU box, from the repo root:  bash profiles/collect_r05.sh OUT
+# with OUT the folder profiles/tools/pmc_passes.sh writes under; then, on any machine:
+#   python profiles/summarize_r05.py OUT
+# Kernel-trace statistics of the bench command (a plain run: timed step only; --full: the whole line with every other
 # config); then counter passes (one counter group per pass, --kernel-trace only, as
 # MI355X_MICROARCH.md prescribes) over the dominant kernel of every BASELINE config that has one of
 # its own: the headline CTC search (C2 shape), the C5 shard decode, the C3 search, C3 with the bigram
 # model in the loop, C4 sparse_image_warp and SpecAugment's one-launch application, and the two step functions (C3).
 set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-mkdir -p gpurun_out/r05
-rocprofv3 --kernel-trace --stats -d gpurun_out/r05/bench_stats -o bench --output-format csv -- \
-  python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extra > gpurun_out/r05/bench_line.json 2> gpurun_out/r05/bench.err
+out=${1:?usage: bash profiles/collect_r05.sh OUT}/r05
+mkdir -p "$out"
+rocprofv3 --kernel-trace --stats -d "$out/bench_stats" -o bench --output-format csv -- \
+  python3 bench.py --steps 10 --warmup 3 > "$out/bench_line.json" 2> "$out/bench.err"
 echo "bench stats done"
-rocprofv3 --kernel-trace --stats -d gpurun_out/r05/bench_full_stats -o bench --output-format csv -- \
-  python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline > gpurun_out/r05/bench_full_line.json 2> gpurun_out/r05/bench_full.err
+rocprofv3 --kernel-trace --stats -d "$out/bench_full_stats" -o bench --output-format csv -- \
+  python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$out/bench_full_line.json" 2> "$out/bench_full.err"
 echo "bench full stats done"
 bash profiles/tools/pmc_passes.sh r05/pmc_headline profiles/prof_ctc.py
 bash profiles/tools/pmc_passes.sh r05/pmc_c5 profiles/prof_ctc_shape.py 512 4096 5000

@@ -8,25 +8,19 @@ dev = torch.device("cuda:0")
 ypl = torch.full((1024, 16), 100, device=dev)
 def old(): return int(ypl.max().item()) >= 100
 def new():
-    flag = _cabi.host_flag()
-    _cabi.lib().pdt_lens_reach(_cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), 1024, 16, 100, flag.ptr, _cabi.stream_ptr(dev))
+    report = _cabi.host_report(dev)
+    _cabi.lib().pdt_lens_reach(_cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), 1024, 16, 100, report.ptr, _cabi.stream_ptr(dev))
     _cabi.stream_synchronize(dev)
-    return bool(flag.value & 1)
+    return bool(report.read() & 1)
 def new_devsync():
-    flag = _cabi.host_flag()
-    _cabi.lib().pdt_lens_reach(_cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), 1024, 16, 100, flag.ptr, _cabi.stream_ptr(dev))
+    report = _cabi.host_report(dev)
+    _cabi.lib().pdt_lens_reach(_cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), 1024, 16, 100, report.ptr, _cabi.stream_ptr(dev))
     torch.cuda.synchronize(dev)
-    return bool(flag.value & 1)
+    return bool(report.read() & 1)
 def new_poll():
-    flag = _cabi.host_flag()
-    _cabi.lib().pdt_lens_reach(_cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), 1024, 16, 100, flag.ptr, _cabi.stream_ptr(dev))
-    a = flag._np
-    t_end = time.perf_counter() + 2e-3
-    while a[0] == 0 and time.perf_counter() < t_end:
-        pass
-    if a[0] == 0:
-        _cabi.stream_synchronize(dev)
-    return bool(a[0] & 1)
+    report = _cabi.host_report(dev)
+    _cabi.lib().pdt_lens_reach(_cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), 1024, 16, 100, report.ptr, _cabi.stream_ptr(dev))
+    return bool(report.wait(2e-3) & 1)
 for name, fn in (("max().item()", old), ("lens_reach + poll", new_poll), ("lens_reach + stream sync", new), ("lens_reach + device sync", new_devsync), ("max().item()", old)):
     assert fn() is True
     for _ in range(20): fn()

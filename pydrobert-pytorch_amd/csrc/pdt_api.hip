@@ -67,7 +67,6 @@ const SwitchName kSwitchNames[] = {
     {"PDT_CTC_EXACT_DIV", &Switches::ctc_exact_div, 0},   {"PDT_CTC_ROWREG", &Switches::ctc_rowreg, 1},
     {"PDT_STEP_WIDE", &Switches::step_wide, 0},           {"PDT_CTC_LEAN_EXTRA", &Switches::ctc_lean_extra, 1},
     {"PDT_CTC_PAIR", &Switches::ctc_pair, 1},             {"PDT_STEP_FLAT", &Switches::step_flat, 1},
-    {"PDT_WALK_TABLE", &Switches::walk_table, 1},
 };
 }  // namespace
 
@@ -115,6 +114,7 @@ extern "C" {
 // 12: pdt_random_walk_advance, pdt_random_walk_step, pdt_random_walk_table; the switch PDT_WALK_TABLE;
 //     then, additively (no existing entry point changed): pdt_feat_deltas, pdt_feat_deltas_backward,
 //     pdt_mvn_stats_workspace_bytes, pdt_mvn_stats, pdt_mvn_apply, pdt_mvn_backward
+//     and, with no entry point changed, the switch PDT_WALK_TABLE moved to the host package (no native code read it)
 int pdt_amd_abi_version(void) { return 12; }
 
 int pdt_amd_set_switch(const char *name, int value) {

@@ -16,8 +16,6 @@ struct Switches {
   int step_flat;       // PDT_STEP_FLAT      1  step functions: one selection over all K' * V candidates (beam) / one list for prefixes that share
                        //                       their extension row (CTC) (0: a sorted list per prefix; same results)
   int ctc_lean_extra;  // PDT_CTC_LEAN_EXTRA 1  CTC frame: one-prefix and tie frames decided beside the lean tier (0: by the full tiers, same results)
-  int walk_table;      // PDT_WALK_TABLE     1  RandomWalk over a LookupLanguageModel: chunks of iterations from the model's dense context
-                       //                       table, one launch each (pdt_random_walk_table; 0: the model scores every iteration; same results)
 };
 
 Switches &switches();

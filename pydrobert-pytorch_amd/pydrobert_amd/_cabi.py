@@ -8,6 +8,7 @@ to load, every operator raises -- there is no fallback path.
 import ctypes
 import os
 import threading
+import time
 
 import torch
 
@@ -263,32 +264,56 @@ def require_hip(*tensors):
     return dev
 
 
-_HOST_FLAGS = threading.local()
-
-
-class HostFlag:
-    """One int32 in pinned host memory: ``ptr`` for a kernel to store to, ``value`` for the host."""
+class HostReport:
+    """Four int32 in pinned host memory that a kernel reports a data-dependent verdict to (the reference
+    reaches one with a reduction, a copy and a synchronisation in FRONT of the work): ``ptr`` for the kernel,
+    ``words`` for the host.  ``armed`` is the device of the launch the words were zeroed for until the host
+    reads them: a launch left in flight by an exception between it and its wait may still store to them, so
+    arming them again first synchronises that device."""
 
     def __init__(self):
-        self._t = torch.zeros(1, dtype=torch.int32, pin_memory=True)
-        self._np = self._t.numpy()  # (a view: reads and writes without torch's indexing machinery)
+        self._t = torch.zeros(4, dtype=torch.int32, pin_memory=True)
+        self.words = self._t.numpy()  # (a view: reads and writes without torch's indexing machinery)
         self.ptr = self._t.data_ptr()
+        self.armed = None
 
-    @property
-    def value(self) -> int:
-        return int(self._np[0])
+    def disarm(self) -> None:
+        """Nothing that was launched stores to the words (an error code, an empty shape, a fallback)."""
+        self.armed = None
+
+    def read(self, i: int = 0) -> int:
+        """Word ``i``, once the caller has synchronised the stream."""
+        self.armed = None
+        return int(self.words[i])
+
+    def wait(self, spin_seconds: float = 5e-4) -> int:
+        """Word 0, which the kernel RELEASES at system scope (non-zero once written): polled for half a
+        millisecond -- pinned host memory is coherent by default, and the interrupt behind hipStreamSynchronize
+        costs ~15 us -- then the stream is synchronised (a non-coherent host allocation, a long queue).  The
+        words stay armed until then: an exception inside the wait leaves the next arming to synchronise."""
+        word = self.words
+        t_end = time.perf_counter() + spin_seconds
+        while word[0] == 0:
+            if time.perf_counter() > t_end:
+                stream_synchronize(self.armed)
+                break
+        self.armed = None  # (the kernel's last store has landed, or its stream has drained)
+        return int(word[0])
 
 
-def host_flag() -> HostFlag:
-    """One word in pinned host memory per host thread, zeroed: a word a kernel raises (a data-dependent
-    verdict the reference reaches with a reduction, a copy and a synchronisation in FRONT of the work)
-    for the host to read once the stream has drained.  A caller synchronises before it returns, so a
-    thread never has two in flight."""
-    flag = getattr(_HOST_FLAGS, "flag", None)
-    if flag is None:
-        flag = _HOST_FLAGS.flag = HostFlag()
-    flag._np[0] = 0
-    return flag
+_HOST_REPORTS = threading.local()
+
+
+def host_report(device) -> HostReport:
+    """This host thread's report words, zeroed and armed for a launch on ``device``."""
+    report = getattr(_HOST_REPORTS, "report", None)
+    if report is None:
+        report = _HOST_REPORTS.report = HostReport()
+    elif report.armed is not None:  # (a launch whose report was never read may still store to the words)
+        torch.cuda.synchronize(report.armed)
+    report.words[:] = 0
+    report.armed = device
+    return report
 
 
 def stream_ptr(device):
@@ -312,21 +337,6 @@ _NO_GUARD = _NoGuard()
 def stream_synchronize(device):
     """hipStreamSynchronize of the current stream of ``device``."""
     torch.cuda.current_stream(device).synchronize()
-
-
-def wait_flag(flag, device, spin_seconds=5e-4):
-    """The value of a word a kernel RELEASES at system scope (non-zero once written): polled for half a
-    millisecond -- pinned host memory is coherent by default, and the interrupt behind hipStreamSynchronize
-    costs ~15 us -- then the stream is synchronised (a non-coherent host allocation, a long queue)."""
-    import time
-
-    word = flag._np
-    t_end = time.perf_counter() + spin_seconds
-    while word[0] == 0:
-        if time.perf_counter() > t_end:
-            stream_synchronize(device)
-            break
-    return int(word[0])
 
 
 def on_device(device):

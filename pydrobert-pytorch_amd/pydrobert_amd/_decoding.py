@@ -8,7 +8,6 @@ Host-side mirror of the reference's ``_decoding.py`` for the operators on the ho
 user-supplied language model.
 """
 import math
-import threading
 import weakref
 from typing import Any, Dict, Optional, Tuple
 
@@ -89,13 +88,15 @@ def _beam_search_advance_impl(
     elif ypl is not None and N * Kp:
         # :133-135 don't make y bigger unless we have to; :139-140 -- the reference's own host read
         # (`y_prev_lens.max()`), as one small kernel that raises a word in pinned host memory
-        flag = _cabi.host_flag()
+        report = _cabi.host_report(device)
         with _cabi.on_device(device):
             rc = _cabi.lib().pdt_lens_reach(
-                _cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), N, Kp, S, flag.ptr, _cabi.stream_ptr(device)
+                _cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), N, Kp, S, report.ptr, _cabi.stream_ptr(device)
             )
-            _cabi.check(rc, "pdt_lens_reach")
-        seen = _cabi.wait_flag(flag, device)
+            if rc:
+                report.disarm()
+                _cabi.check(rc, "pdt_lens_reach")
+        seen = report.wait()
         if S:
             grow = bool(seen & 1)
         elif seen & 2:
@@ -721,8 +722,7 @@ class CTCPrefixSearch(torch.nn.Module):
             return False
         if logits.dtype != torch.float:
             return False
-        shift = 0 if (0 <= lm.sos < lm.vocab_size) else 1
-        if lm.succ_start.numel() != lm.vocab_size + shift + 2 or lm.logps.device != logits.device:
+        if lm.succ_start.numel() != lm.vocab_size + lm.shift + 2 or lm.logps.device != logits.device:
             return False
         return not (torch.is_grad_enabled() and logits.requires_grad)
 
@@ -737,7 +737,6 @@ class CTCPrefixSearch(torch.nn.Module):
         T, N, V = probs.size(0), probs.size(1), probs.size(2) - 1
         device = _cabi.require_hip(probs, lens, *_lm_buffers(lm))
         probs = _f32(probs)
-        shift = 0 if (0 <= lm.sos < V) else 1
         L = _cabi.lib()
         with torch.cuda.device(device):
             y = torch.empty((n_frames, N, W), device=device, dtype=torch.long)
@@ -745,14 +744,14 @@ class CTCPrefixSearch(torch.nn.Module):
             nb = torch.empty((N, W), device=device, dtype=torch.float)
             b = torch.empty((N, W), device=device, dtype=torch.float)
             if N:
-                ws_bytes = int(L.pdt_ctc_lookup_lm_search_workspace_bytes(n_frames, N, V, W, lm.max_ngram, V + shift + 1))
+                ws_bytes = int(L.pdt_ctc_lookup_lm_search_workspace_bytes(n_frames, N, V, W, lm.max_ngram, V + lm.shift + 1))
                 ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8)
                 lens_dev = None if lens is None else _i64(lens).contiguous()
                 rc = L.pdt_ctc_lookup_lm_search(
                     _cabi.ptr(probs), probs.stride(0), probs.stride(1), probs.stride(2), _cabi.ptr(lens_dev),
                     n_frames, N, V, W, _cabi.ptr(lm.logps), _cabi.ptr(lm.logbs), _cabi.ptr(lm.child_start),
                     _cabi.ptr(lm.ids_wide), _cabi.ptr(lm.succ_start), _cabi.ptr(lm.succ_tok),
-                    _cabi.ptr(lm.succ_node), lm.max_ngram, V + shift + 1, lm.sos, float(self.beta),
+                    _cabi.ptr(lm.succ_node), lm.max_ngram, V + lm.shift + 1, lm.sos, float(self.beta),
                     int(self.valid_mixture), _cabi.ptr(y), _cabi.ptr(y_lens), _cabi.ptr(nb), _cabi.ptr(b),
                     _cabi.ptr(ws), ws_bytes, _cabi.stream_ptr(device),
                 )  # fmt: skip
@@ -919,31 +918,40 @@ def _identity_of(*tensors):
         return None
 
 
-# dense tables of bigram LookupLanguageModels, per model object (BeamSearch._bigram_table)
+# dense tables of LookupLanguageModels, per model object: a bigram model's (_dense_table: BeamSearch's and
+# RandomWalk's), those of order 3 and up (_dense_table: RandomWalk's), and the factor table of the last mix
+# CTCPrefixSearch searched a model with (_factor_table)
 _BIGRAM_TABLES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-# ... and the factor tables of the mixes they have been searched with (_factor_table)
+_CONTEXT_TABLES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 _FACTOR_TABLES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
+_DENSE_TABLE_MAX_BYTES = 64 << 20  # (the table stays in the 256 MiB Infinity Cache)
 _FACTOR_TABLE_MAX_BYTES = 6 << 30  # (a trigram model over 1000 tokens: 4 GB of this card's 288)
 
 
-def _bigram_scores(lm: "LookupLanguageModel", device: torch.device):
-    """``(scores (U, V) float32, sos_row)`` of a bigram model: row ``c`` = its scores after context
-    token ``c`` (the start-of-sequence token's row last when it lies outside the vocabulary) -- one
-    call of the model's own scoring kernel over every context."""
-    scores, sos_row, _ = _context_scores(lm, device, 2)
-    return scores, sos_row
+def _cached_table(cache, lm: "LookupLanguageModel", device: torch.device, build, *params):
+    """``cache[lm]``'s table when it was built on ``device`` with ``params`` from every trie buffer of ``lm``
+    as it is now (the same tensor at the same version), else ``build()``'s, kept in its place.  Models whose
+    buffers carry no version counter -- built under inference_mode -- get a fresh table per call.  Writes the
+    counter does not see (``.data``, raw pointers) are the caller's to announce: ``del cache[lm]``."""
+    ident = _identity_of(*_lm_buffers(lm))
+    key = None if ident is None else (ident, str(device)) + params
+    ent = cache.get(lm)
+    if key is not None and ent is not None and ent[0] == key:
+        return ent[1:]
+    table = build()
+    if key is not None:
+        cache[lm] = (key,) + table
+    return table
 
 
-def _context_scores(lm: "LookupLanguageModel", device: torch.device, order: Optional[int] = None):
-    """``(scores (U^(order-1), V) float32, sos_row, U)``: the model's scores after EVERY context of
-    ``order - 1`` symbols -- row ``r`` = the context whose symbols are the digits of ``r`` in base ``U``,
-    oldest first; the symbols are the V tokens, then the start-of-sequence token when it lies outside the
-    vocabulary (``U = V + 1``); ``sos_row`` = the all-sos context of the empty prefix (the reference pads
-    short histories with sos, _lm.py:403-515).  One call of the model's own scoring kernel."""
-    V = lm.vocab_size
-    order = lm.max_ngram if order is None else order
-    shift = 0 if (0 <= lm.sos < V) else 1
-    U, n1 = V + shift, order - 1
+def _context_scores(lm: "LookupLanguageModel", device: torch.device):
+    """``(scores (U^(n-1), V) float32, sos_row, U)`` of an n-gram model: its scores after EVERY context of
+    ``n - 1`` symbols -- row ``r`` = the context whose symbols are the digits of ``r`` in base ``U``, oldest
+    first; the symbols are the V tokens, then the start-of-sequence token when it lies outside the vocabulary
+    (``U = V + 1``); ``sos_row`` = the all-sos context of the empty prefix (the reference pads short
+    histories with sos, _lm.py:403-515).  One call of the model's own scoring kernel."""
+    V, shift = lm.vocab_size, lm.shift
+    U, n1 = V + shift, lm.max_ngram - 1
     sos_sym = lm.sos if shift == 0 else V
     with torch.no_grad():
         rows = torch.arange(U**n1, device=device)
@@ -956,29 +964,50 @@ def _context_scores(lm: "LookupLanguageModel", device: torch.device, order: Opti
     return _f32(table).contiguous(), sos_row, U
 
 
+def _dense_table(lm: "LookupLanguageModel", device: torch.device):
+    """``(table (U^(n-1), V), stats (U^(n-1), 2), sos_row, U)`` of an n-gram :class:`LookupLanguageModel`
+    whose dense context table (_context_scores) stays within _DENSE_TABLE_MAX_BYTES on ``device``, else
+    ``None``; ``stats`` = every row's maximum and log-sum-exp (pdt_row_log_softmax_stats).  Built once per
+    model and device, kept while the model's buffers are unchanged (_cached_table)."""
+    V = lm.vocab_size
+    U, n1 = V + lm.shift, lm.max_ngram - 1
+    if n1 < 1 or (U**n1) * V * 4 > _DENSE_TABLE_MAX_BYTES or lm.logps.device != device:
+        return None
+
+    def build():
+        table, sos_row, _ = _context_scores(lm, device)
+        R = table.size(0)
+        with torch.no_grad():
+            stats = torch.empty((R, 2), device=device, dtype=torch.float)
+            with torch.cuda.device(device):
+                rc = _cabi.lib().pdt_row_log_softmax_stats(
+                    _cabi.ptr(table), table.stride(0), table.stride(1), R, V, _cabi.ptr(stats),
+                    _cabi.stream_ptr(device),
+                )
+            _cabi.check(rc, "pdt_row_log_softmax_stats")
+        return table, stats, sos_row, U
+
+    return _cached_table(_BIGRAM_TABLES if n1 == 1 else _CONTEXT_TABLES, lm, device, build)
+
+
 def _factor_table(lm: "LookupLanguageModel", beta: float, valid_mixture: bool, device: torch.device):
     """``(factors (rows, V), row maxima (rows,), sos_row, U)``: the model's factor of CTCPrefixSearch's mix for
     every context (include/pdt_amd.h: pdt_lm_factor_table), built once per model, mix and device and kept
-    while every trie buffer of the model is the same tensor at the same version (see
-    BeamSearch._bigram_table for what that does not see).  The factors overwrite the scores they are
+    while the model's buffers are unchanged (_cached_table).  The factors overwrite the scores they are
     formed from (a trigram model's table is gigabytes)."""
-    ident = _identity_of(*_lm_buffers(lm))
-    key = None if ident is None else (ident, str(device), float(beta), bool(valid_mixture))
-    ent = _FACTOR_TABLES.get(lm)
-    if key is not None and ent is not None and ent[0] == key:
-        return ent[1], ent[2], ent[3], ent[4]
-    factors, sos_row, U = _context_scores(lm, device)
-    rows, V = factors.shape
-    with torch.cuda.device(device):
-        rc = _cabi.lib().pdt_lm_factor_table(
-            _cabi.ptr(factors), rows, V, float(beta), int(valid_mixture), _cabi.ptr(factors), factors.stride(0),
-            _cabi.stream_ptr(device),
-        )
-    _cabi.check(rc, "pdt_lm_factor_table")
-    fmax = factors.max(1)[0].contiguous()
-    if key is not None:
-        _FACTOR_TABLES[lm] = (key, factors, fmax, sos_row, U)
-    return factors, fmax, sos_row, U
+
+    def build():
+        factors, sos_row, U = _context_scores(lm, device)
+        rows, V = factors.shape
+        with torch.cuda.device(device):
+            rc = _cabi.lib().pdt_lm_factor_table(
+                _cabi.ptr(factors), rows, V, float(beta), int(valid_mixture), _cabi.ptr(factors), factors.stride(0),
+                _cabi.stream_ptr(device),
+            )
+        _cabi.check(rc, "pdt_lm_factor_table")
+        return factors, factors.max(1)[0].contiguous(), sos_row, U
+
+    return _cached_table(_FACTOR_TABLES, lm, device, build, float(beta), bool(valid_mixture))
 
 
 class BeamSearch(torch.nn.Module):
@@ -1063,49 +1092,23 @@ class BeamSearch(torch.nn.Module):
 
     @torch.jit.unused
     def _bigram_table(self, device: torch.device):
-        """``(table (U, V), stats (U, 2), sos_row)`` for a bigram :class:`LookupLanguageModel` whose dense
-        table stays below 64 MiB, else ``None``: row ``c`` holds the model's scores after context token
-        ``c`` (one call of its own scoring kernel over every context, made once per model and device and
-        kept while the model's buffers are unchanged), ``stats`` every row's maximum and log-sum-exp.
-        An iteration of the search then reads its prefixes' rows straight from the table
-        (``pdt_beam_search_step_table``) instead of having the model write ``(N K, V)`` scores first."""
+        """``(table (U, V), stats (U, 2), sos_row, U)`` of a bigram :class:`LookupLanguageModel` whose dense
+        table stays within 64 MiB (_dense_table), else ``None``: row ``c`` holds the model's scores after
+        context token ``c``, ``stats`` every row's maximum and log-sum-exp.  An iteration of the search then
+        reads its prefixes' rows straight from the table (``pdt_beam_search_step_table``) instead of having
+        the model write ``(N K, V)`` scores first.  (PDT_BEAM_TABLE=0 or ``del _BIGRAM_TABLES[lm]`` after a
+        write the buffers' version counters do not see.)"""
         lm = self.lm
         if type(lm) is not LookupLanguageModel or lm.max_ngram != 2 or not switches.get("PDT_BEAM_TABLE"):
             return None
-        V = lm.vocab_size
-        shift = 0 if (0 <= lm.sos < V) else 1
-        U = V + shift
-        if U * V * 4 > (64 << 20) or lm.logps.device != device:
-            return None
-        # (kept while EVERY trie buffer is the same tensor at the same version; models whose buffers carry
-        # no version counter -- built under inference_mode -- get a fresh table per search.  Writes the
-        # counter does not see (`.data`, raw pointers) are the caller's to announce: `del
-        # _BIGRAM_TABLES[lm]` or PDT_BEAM_TABLE=0)
-        ident = _identity_of(*_lm_buffers(lm))
-        key = None if ident is None else (ident, str(device))
-        ent = _BIGRAM_TABLES.get(lm)
-        if key is not None and ent is not None and ent[0] == key:
-            return ent[1], ent[2], ent[3]
-        table, _ = _bigram_scores(lm, device)
-        with torch.no_grad():
-            stats = torch.empty((U, 2), device=device, dtype=torch.float)
-            with torch.cuda.device(device):
-                rc = _cabi.lib().pdt_row_log_softmax_stats(
-                    _cabi.ptr(table), table.stride(0), table.stride(1), U, V, _cabi.ptr(stats),
-                    _cabi.stream_ptr(device),
-                )
-            _cabi.check(rc, "pdt_row_log_softmax_stats")
-        sos_row = lm.sos if shift == 0 else V
-        if key is not None:
-            _BIGRAM_TABLES[lm] = (key, table, stats, sos_row)
-        return table, stats, sos_row
+        return _dense_table(lm, device)
 
     @torch.jit.unused
     def _table_search(self, dense, N: int, max_iters: int, squeeze: bool):
         """``pdt_beam_search_table`` + ``pdt_beam_search_table_paths``: the whole search in one launch, the
         paths written once at the end (one host read in between: the number of rows ``y`` has).  ``None``
         when the kernel does not take the shape."""
-        table, stats, sos_row = dense
+        table, stats, sos_row, _ = dense
         device, W, V = table.device, self.width, self.lm.vocab_size
         L = _cabi.lib()
         with _cabi.on_device(device):
@@ -1135,7 +1138,7 @@ class BeamSearch(torch.nn.Module):
 
     @torch.jit.unused
     def _forward_fused(
-        self, prev: Dict[str, torch.Tensor], batch_size: Optional[int], max_iters: Optional[int]
+        self, prev: Dict[str, torch.Tensor], batch_size: Optional[int], max_iters: int
     ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
         """The search with every iteration's bookkeeping in ONE kernel (csrc/beam_step.hip) around the
         language model's forward: no ``log_softmax`` / ``masked_fill`` / ``where`` passes over
@@ -1158,12 +1161,6 @@ class BeamSearch(torch.nn.Module):
             return None
         N = 1 if batch_size is None else batch_size
         V, W = self.lm.vocab_size, self.width
-        if max_iters is None:
-            if self.eos is None:
-                raise RuntimeError("max_iters must be set when eos is unset")
-            max_iters = 1073741824
-        elif max_iters < 0:
-            raise RuntimeError("max_iters must be non-negative, got {}".format(max_iters))
         L = _cabi.lib()
         has_eos = self.eos is not None
         y = torch.empty((0, N), dtype=torch.long, device=device)
@@ -1197,71 +1194,48 @@ class BeamSearch(torch.nn.Module):
             done = self._table_search(dense, N, max_iters, batch_size is None)
             if done is not None:
                 return done
-        first_rows = None if dense is None else torch.full((N, 1), dense[2], dtype=torch.long, device=device)
-        if dense is not None:  # (what does not change from one iteration to the next, once)
-            table, stats, _ = dense
-            table_args = (_cabi.ptr(table), table.stride(0), table.stride(1), table.size(0), _cabi.ptr(stats))
-            eos_args = (int(has_eos), int(self.eos or 0), int(self.finish_all_paths), int(self.pad_value))
-            counts_ptr, pad_from_ptr, stream = counts.data_ptr(), _cabi.ptr(pad_from), _cabi.stream_ptr(device)
-            step_table = L.pdt_beam_search_step_table
+        # (what does not change from one iteration to the next, once)
+        eos_args = (int(has_eos), int(self.eos or 0), int(self.finish_all_paths), int(self.pad_value))
+        counts_ptr, pad_from_ptr, stream = counts.data_ptr(), pad_from.data_ptr(), _cabi.stream_ptr(device)
+        if dense is not None:
+            table, stats, sos_row, _ = dense
+            table_args = (table.data_ptr(), table.stride(0), table.stride(1), table.size(0), stats.data_ptr())
+            first_rows = torch.full((N, 1), sos_row, dtype=torch.long, device=device)
         while t < max_iters:
-            if dense is not None:
-                # a bigram table model: the prefixes' rows of its dense table, by their last tokens
-                rows = first_rows if t == 0 else y[t - 1]
-                with _cabi.on_device(device):
-                    y_new = torch.empty((t + 1, N, W), dtype=torch.long, device=device)
-                    lens_new = torch.empty((N, W), dtype=torch.long, device=device)
-                    lp_new = torch.empty((N, W), device=device)
-                    src = torch.empty((N, W), dtype=torch.long, device=device)
-                    rc = step_table(
-                        *table_args, rows.data_ptr(), N, Kp, V, W,
-                        log_probs.data_ptr(), log_probs.stride(0), log_probs.stride(1),
-                        y.data_ptr(), t, y.stride(0), y.stride(1), y.stride(2),
-                        lens.data_ptr(), lens.stride(0), lens.stride(1), *eos_args,
-                        y_new.data_ptr(), lens_new.data_ptr(), lp_new.data_ptr(), src.data_ptr(),
-                        counts_ptr + 4 * (t % check_every), pad_from_ptr, stream,
-                    )  # fmt: skip
-                if rc:
-                    _cabi.check(rc, "pdt_beam_search_step_table")
-                y, lens, log_probs, Kp = y_new, lens_new, lp_new, W
-                t += 1
-                if has_eos and (t % check_every == 0 or t == max_iters):
-                    seen = counts.tolist()
-                    lo = t - ((t - 1) % check_every + 1)
-                    for i in range(lo, t):
-                        if i > 0 and seen[i % check_every] == 0:
-                            t_stop = i
-                            break
-                    if t_stop >= 0:
-                        break
-                    counts.zero_()
-                continue
-            if t and t % 1024 == 0:
-                steps = torch.arange(t, t + 1024, device=device)
-            scores, state_next = self.lm.calc_idx_log_probs(y.flatten(1), prev, steps[t % 1024])
-            if torch.is_grad_enabled() and scores.requires_grad:
-                if t == 0:  # (a model whose weights are no registered parameters: the differentiable loop)
-                    return None
-                raise RuntimeError("BeamSearch: the language model's output wants gradients inside a search "
-                                   "that was started without any (set PDT_BEAM_FUSED=0)")
-            out_dtype = scores.dtype
-            scores = _f32(scores).reshape(N, Kp, V)
-            with torch.cuda.device(device):
+            if dense is None:  # the model's scores of every prefix
+                if t and t % 1024 == 0:
+                    steps = torch.arange(t, t + 1024, device=device)
+                scores, state_next = self.lm.calc_idx_log_probs(y.flatten(1), prev, steps[t % 1024])
+                if torch.is_grad_enabled() and scores.requires_grad:
+                    if t == 0:  # (a model whose weights are no registered parameters: the differentiable loop)
+                        return None
+                    raise RuntimeError("BeamSearch: the language model's output wants gradients inside a search "
+                                       "that was started without any (set PDT_BEAM_FUSED=0)")
+                out_dtype = scores.dtype
+                scores = _f32(scores).reshape(N, Kp, V)
+            with _cabi.on_device(device):
                 y_new = torch.empty((t + 1, N, W), dtype=torch.long, device=device)
                 lens_new = torch.empty((N, W), dtype=torch.long, device=device)
                 lp_new = torch.empty((N, W), device=device)
                 src = torch.empty((N, W), dtype=torch.long, device=device)
-                rc = L.pdt_beam_search_step(
-                    _cabi.ptr(scores), scores.stride(0), scores.stride(1), scores.stride(2), N, Kp, V, W,
-                    _cabi.ptr(log_probs), log_probs.stride(0), log_probs.stride(1),
-                    _cabi.ptr(y), t, y.stride(0), y.stride(1), y.stride(2),
-                    _cabi.ptr(lens), lens.stride(0), lens.stride(1), int(has_eos), int(self.eos or 0),
-                    int(self.finish_all_paths), int(self.pad_value), _cabi.ptr(y_new), _cabi.ptr(lens_new),
-                    _cabi.ptr(lp_new), _cabi.ptr(src), counts.data_ptr() + 4 * (t % check_every),
-                    _cabi.ptr(pad_from), _cabi.stream_ptr(device),
+                state_args = (
+                    log_probs.data_ptr(), log_probs.stride(0), log_probs.stride(1),
+                    y.data_ptr(), t, y.stride(0), y.stride(1), y.stride(2),
+                    lens.data_ptr(), lens.stride(0), lens.stride(1), *eos_args,
+                    y_new.data_ptr(), lens_new.data_ptr(), lp_new.data_ptr(), src.data_ptr(),
+                    counts_ptr + 4 * (t % check_every), pad_from_ptr, stream,
                 )  # fmt: skip
-            _cabi.check(rc, "pdt_beam_search_step")
-            prev = self.lm.extract_by_src(state_next, (src + row_base[Kp]).flatten())
+                if dense is not None:  # a bigram table model: the prefixes' rows of its table, by their last tokens
+                    rows = first_rows if t == 0 else y[t - 1]
+                    rc = L.pdt_beam_search_step_table(*table_args, rows.data_ptr(), N, Kp, V, W, *state_args)
+                else:
+                    rc = L.pdt_beam_search_step(
+                        scores.data_ptr(), scores.stride(0), scores.stride(1), scores.stride(2), N, Kp, V, W, *state_args
+                    )
+            if rc:
+                _cabi.check(rc, "pdt_beam_search_step" if dense is None else "pdt_beam_search_step_table")
+            if dense is None:
+                prev = self.lm.extract_by_src(state_next, (src + row_base[Kp]).flatten())
             y, lens, log_probs, Kp = y_new, lens_new, lp_new, W
             t += 1
             if has_eos and (t % check_every == 0 or t == max_iters):
@@ -1301,6 +1275,12 @@ class BeamSearch(torch.nn.Module):
         device = self.device_buffer.device
         N = 1 if batch_size is None else batch_size
         V, W = self.lm.vocab_size, self.width
+        if max_iters is None:
+            if self.eos is None:
+                raise RuntimeError("max_iters must be set when eos is unset")
+            max_iters = 1073741824
+        elif max_iters < 0:
+            raise RuntimeError("max_iters must be non-negative, got {}".format(max_iters))
         if not torch.jit.is_scripting():
             fused = self._forward_fused(prev, batch_size, max_iters)
             if fused is not None:
@@ -1311,12 +1291,6 @@ class BeamSearch(torch.nn.Module):
         y = y.unsqueeze(2)
         log_probs = torch.full((N, Kp), -math.log(Kp), device=device)
         lens = torch.zeros((N, Kp), dtype=torch.long, device=device)
-        if max_iters is None:
-            if self.eos is None:
-                raise RuntimeError("max_iters must be set when eos is unset")
-            max_iters = 1073741824
-        elif max_iters < 0:
-            raise RuntimeError("max_iters must be non-negative, got {}".format(max_iters))
         pad_row = torch.full((1, N, W), self.pad_value, device=device, dtype=torch.long)
         track_eos = self.eos is not None
         for t in range(max_iters):
@@ -1581,36 +1555,26 @@ def sequence_log_probs(
     raise RuntimeError("logits must be either a Tensor or PackedSequence")
 
 
-class _WalkWords:
-    """Three int32 in pinned host memory a random-walk kernel reports to (include/pdt_amd.h, "Random
-    walks"): [0] PDT_WALK_DONE | bits, stored last; [1] walks still live; [2] the longest walk."""
-
-    def __init__(self):
-        self._t = torch.zeros(4, dtype=torch.int32, pin_memory=True)
-        self._np = self._t.numpy()
-        self.ptr = self._t.data_ptr()
-
-
-_WALK_WORDS = threading.local()
 _WALK_INVALID, _WALK_REACH, _WALK_BAD_LENS = 2, 4, 8
 
 
 def _walk_launch(device: torch.device, launch, what: str) -> Tuple[int, int, int]:
-    """``launch(host_words_ptr)`` enqueues one random-walk kernel; returns its report ``(bits, live,
-    longest)`` once it is done (one wait on a word in pinned host memory, no device-to-host copy).  A row
-    the kernel could draw nothing from raises (the reference's sampler would hit a device assert)."""
-    words = getattr(_WALK_WORDS, "w", None)
-    if words is None:
-        words = _WALK_WORDS.w = _WalkWords()
-    words._np[:] = 0
-    _cabi.check(launch(words.ptr), what)
-    bits = _cabi.wait_flag(words, device)
+    """``launch(host_report_ptr)`` enqueues one random-walk kernel; returns its report ``(bits, live,
+    longest)`` once it is done (include/pdt_amd.h, "Random walks": word 0 = PDT_WALK_DONE | bits, stored
+    last; one wait on it in pinned host memory, no device-to-host copy).  A row the kernel could draw
+    nothing from raises (the reference's sampler would hit a device assert)."""
+    report = _cabi.host_report(device)
+    rc = launch(report.ptr)
+    if rc:
+        report.disarm()
+        _cabi.check(rc, what)
+    bits = report.wait()
     if bits & _WALK_INVALID:
         raise RuntimeError(
             "{}: a row of log-probabilities has no positive finite mass (every entry -inf, a NaN or +inf); "
             "nothing can be sampled from it".format(what)
         )
-    return bits, int(words._np[1]), int(words._np[2])
+    return bits, report.read(1), report.read(2)
 
 
 def _random_walk_checks(
@@ -1838,51 +1802,11 @@ class SequenceLogProbabilities(torch.nn.Module):
         return sequence_log_probs(logits, hyp, self.dim, self.eos)
 
 
-# dense context tables of LookupLanguageModels of order 3 and up, per model object (RandomWalk; a bigram
-# model's table is the one BeamSearch keeps in _BIGRAM_TABLES)
-_CONTEXT_TABLES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-_WALK_TABLE_MAX_BYTES = 64 << 20  # (the table stays in the 256 MiB Infinity Cache)
-
-
-def _walk_table(lm: "LookupLanguageModel", device: torch.device):
-    """``(table (U^(n-1), V), stats (U^(n-1), 2), sos_row, U)`` of an n-gram :class:`LookupLanguageModel`
-    whose dense context table (_context_scores) stays within 64 MiB, else ``None``; ``stats`` = every
-    row's maximum and log-sum-exp (pdt_row_log_softmax_stats).  Built once per model and device and kept
-    while every trie buffer is the same tensor at the same version, as BeamSearch._bigram_table (which
-    shares the bigram tables)."""
-    V = lm.vocab_size
-    shift = 0 if (0 <= lm.sos < V) else 1
-    U, n1 = V + shift, lm.max_ngram - 1
-    if n1 < 1 or (U**n1) * V * 4 > _WALK_TABLE_MAX_BYTES or lm.logps.device != device:
-        return None
-    cache = _BIGRAM_TABLES if n1 == 1 else _CONTEXT_TABLES
-    ident = _identity_of(*_lm_buffers(lm))
-    key = None if ident is None else (ident, str(device))
-    ent = cache.get(lm)
-    if key is not None and ent is not None and ent[0] == key:
-        return ent[1], ent[2], ent[3], U
-    table, sos_row, _ = _context_scores(lm, device)
-    R = table.size(0)
-    with torch.no_grad():
-        stats = torch.empty((R, 2), device=device, dtype=torch.float)
-        with torch.cuda.device(device):
-            rc = _cabi.lib().pdt_row_log_softmax_stats(
-                _cabi.ptr(table), table.stride(0), table.stride(1), R, V, _cabi.ptr(stats), _cabi.stream_ptr(device)
-            )
-        _cabi.check(rc, "pdt_row_log_softmax_stats")
-    if key is not None:
-        cache[lm] = (key, table, stats, sos_row)
-    return table, stats, sos_row, U
-
-
-def _walk_chunks(max_iters: int):
-    """The iterations ``[t, t + C)`` whose uniforms one ``torch.rand((C, N))`` call draws: C = 64, then
-    doubling up to 4096, cut off at ``max_iters`` -- every route of RandomWalk draws on this schedule."""
-    t, C = 0, 64
-    while t < max_iters:
-        c = min(C, max_iters - t)
-        yield t, c
-        t, C = t + c, min(2 * C, 4096)
+def _walk_chunk(t: int, max_iters: int) -> int:
+    """How many iterations from ``t``, the first of a chunk, one ``torch.rand((C, N))`` call draws the
+    uniforms of: C = 64, doubling up to 4096 (the chunks start at 0, 64, 192, 448, ...: C = t + 64 until
+    then), cut off at ``max_iters`` -- every route of RandomWalk draws on this schedule."""
+    return min(min(t + 64, 4096), max_iters - t)
 
 
 class RandomWalk(torch.nn.Module):
@@ -1951,7 +1875,7 @@ class RandomWalk(torch.nn.Module):
             return None
         if torch.is_grad_enabled() and any(p.requires_grad for p in lm.parameters()):
             return None
-        dense = _walk_table(lm, device)
+        dense = _dense_table(lm, device)
         if dense is None:
             return None
         table, stats, sos_row, U = dense
@@ -1965,8 +1889,9 @@ class RandomWalk(torch.nn.Module):
             lp = torch.zeros((N,), device=device, dtype=torch.float)
             ctl = torch.zeros((4,), device=device, dtype=torch.int32)
             y = torch.empty((0, N), device=device, dtype=torch.long)
-            longest, stream = 0, _cabi.stream_ptr(device)
-            for t, C in _walk_chunks(max_iters):
+            t, longest, stream = 0, 0, _cabi.stream_ptr(device)
+            while t < max_iters:
+                C = _walk_chunk(t, max_iters)
                 u = torch.rand((C, N), device=device, dtype=torch.float)
                 y_new = torch.empty((t + C, N), device=device, dtype=torch.long)
                 y_new[:t] = y
@@ -1982,6 +1907,7 @@ class RandomWalk(torch.nn.Module):
                 )  # fmt: skip
                 if has_eos and live == 0:
                     break
+                t += C
         # the reference leaves its loop at the first iteration that finds every walk ended
         T = min(max_iters, longest) if has_eos else max_iters
         return y[:T], lens, lp
@@ -2055,7 +1981,7 @@ class RandomWalk(torch.nn.Module):
         # (pydrobert_amd::random_walk_step) with the default hook and an output that wants no gradient, else the
         # reference's log_softmax / hook / eos masking and pydrobert_amd::random_walk_advance.  The uniforms of
         # iterations [t, t + C) come from one torch.rand((C, N)) after the model's call of iteration t (the
-        # chunks of _walk_chunks), and y grows by the chunk.  The one host read per iteration -- whether some
+        # chunks of _walk_chunk), and y grows by the chunk.  The one host read per iteration -- whether some
         # walk is still live -- comes back with the step's kernel: the model is called exactly as often as
         # under the reference.
         device = self.device_buffer.device
@@ -2068,16 +1994,15 @@ class RandomWalk(torch.nn.Module):
         u = torch.empty((0, N), device=device)
         fused = self.default_hook
         out_dtype = log_probs.dtype
-        live, u_from, u_to, chunk, T = N, 0, 0, 64, 0
+        live, u_from, u_to, T = N, 0, 0, 0
         for t in range(max_iters):
             if self.eos is not None and live == 0:
                 break
             t_ = torch.tensor(t, device=device)
             lp_t, prev = self.lm.calc_idx_log_probs(y[:t], prev, t_)
             if t == u_to:
-                C = min(chunk, max_iters - t)
-                u = torch.rand((C, N), device=device, dtype=torch.float)
-                u_from, u_to, chunk = t, t + C, min(2 * chunk, 4096)
+                u_from, u_to = t, t + _walk_chunk(t, max_iters)
+                u = torch.rand((u_to - t, N), device=device, dtype=torch.float)
                 y_new = torch.empty((u_to, N), device=device, dtype=torch.long)
                 y_new[:t] = y[:t]
                 y = y_new

@@ -941,24 +941,26 @@ def _spec_augment_apply_warp_op(
     # ``check_lengths``: the reference's "values of lengths must be between (1, T)" (_img.py:1037-1041)
     # decided by the kernel that reads the lengths -- a word in pinned host memory, looked at once the
     # stream has drained -- instead of four small kernels, a copy and a synchronisation in front of it
-    flag = _cabi.host_flag() if (check_lengths and lens is not None) else None
+    report = _cabi.host_report(device) if (check_lengths and lens is not None) else None
     with torch.cuda.device(device):
         out = torch.empty((N, T, F), device=device, dtype=torch.float)
         rc = _cabi.lib().pdt_spec_augment_apply_warp(
             _cabi.ptr(x), N, T, F, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(src), _cabi.ptr(flow),
             _cabi.ptr(lens), int(interpolation_order), _cabi.ptr(t_0), _cabi.ptr(t), mt, _cabi.ptr(f_0), _cabi.ptr(f), mf,
-            _cabi.ptr(out), 0 if flag is None else flag.ptr, _cabi.stream_ptr(device),
+            _cabi.ptr(out), 0 if report is None else report.ptr, _cabi.stream_ptr(device),
         )  # fmt: skip
+    if report is not None and (rc or not (N and T and F)):
+        report.disarm()  # (no kernel was launched)
     if rc == _cabi.PDT_E_UNSUPPORTED:
-        if flag is not None:
+        if report is not None:
             _spec_augment_raise_unless(torch.all((lens <= T) & (lens > 0)), T)
         ln = lens if lens is not None else torch.full((N,), T, dtype=torch.long, device=device)
         tgrid = torch.ops.pydrobert_amd.warp_1d_grid(src, flow, ln, T, interpolation_order)
         return torch.ops.pydrobert_amd.spec_augment_apply(feats, tgrid, None, t_0, t, f_0, f)
     _cabi.check(rc, "pdt_spec_augment_apply_warp")
-    if flag is not None and N and T and F:
+    if report is not None and N and T and F:
         torch.cuda.current_stream(device).synchronize()
-        if flag.value != 0:
+        if report.read() != 0:
             raise RuntimeError("values of lengths must be between (1, {})".format(T))
     return out.to(feats.dtype)
 
@@ -1022,7 +1024,6 @@ def _spec_augment_forward_op(
         if lens.dtype != torch.long or not lens.is_contiguous():
             lens = lens.long().contiguous()
     L = _cabi.lib()
-    flag = _cabi.host_flag() if lens is not None else None
     with torch.cuda.device(device):
         stream = _cabi.stream_ptr(device)
         w_0, w = (torch.empty((N,), device=device, dtype=torch.float) for _ in range(2))
@@ -1037,20 +1038,23 @@ def _spec_augment_forward_op(
             _cabi.ptr(f_0) if fm else 0, _cabi.ptr(f) if fm else 0, stream,
         )  # fmt: skip
         _cabi.check(rc, "pdt_spec_augment_draw")
+        report = _cabi.host_report(device) if lens is not None else None
         rc = L.pdt_spec_augment_apply_warp(
             _cabi.ptr(x), N, T, F, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(w_0), _cabi.ptr(w),
             _cabi.ptr(lens), int(interpolation_order), _cabi.ptr(t_0) if tm else 0, _cabi.ptr(t) if tm else 0,
             num_time_mask if tm else 0, _cabi.ptr(f_0) if fm else 0, _cabi.ptr(f) if fm else 0,
-            num_freq_mask if fm else 0, _cabi.ptr(out), 0 if flag is None else flag.ptr, stream,
+            num_freq_mask if fm else 0, _cabi.ptr(out), 0 if report is None else report.ptr, stream,
         )  # fmt: skip
+    if report is not None and (rc or not (N and T and F)):
+        report.disarm()  # (no kernel was launched)
     if rc == _cabi.PDT_E_UNSUPPORTED:  # (a layout the one-pass kernel does not take: through the grid)
         out = _spec_augment_apply(feats, (w_0, w, torch.empty(0), torch.empty(0), t_0, t, f_0, f), interpolation_order,
                                   lengths, True)
         return [out, w_0, w, t_0, t, f_0, f]
     _cabi.check(rc, "pdt_spec_augment_apply_warp")
-    if flag is not None and N and T and F:
+    if report is not None and N and T and F:
         torch.cuda.current_stream(device).synchronize()
-        if flag.value != 0:
+        if report.read() != 0:
             raise RuntimeError("values of lengths must be between (1, {})".format(T))
     return [out.to(feats.dtype), w_0, w, t_0, t, f_0, f]
 

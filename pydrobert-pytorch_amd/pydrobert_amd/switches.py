@@ -25,11 +25,12 @@ _HOST_DEFAULTS = {
     "PDT_BEAM_SEARCH": 1,  # ... and every iteration from ONE launch, the paths read off a trie at the end (csrc/beam_step.hip)
     "PDT_BEAM_TABLE": 1,  # BeamSearch over a bigram LookupLanguageModel reads its dense table
     "PDT_CHECK_INVARIANTS": 0,  # BeamSearch's loop checks that the history grows (a host read per iteration)
+    "PDT_WALK_TABLE": 1,  # RandomWalk over a LookupLanguageModel: chunks of iterations over its dense context table, one launch each
 }
 # switches of the native library (csrc/switches.hpp); the library reads the environment itself
 _NATIVE = (
     "PDT_LEV_BITPAR", "PDT_OC_BITPAR", "PDT_CTC_EXACT_DIV", "PDT_CTC_ROWREG", "PDT_STEP_WIDE",
-    "PDT_CTC_LEAN_EXTRA", "PDT_CTC_PAIR", "PDT_STEP_FLAT", "PDT_WALK_TABLE",
+    "PDT_CTC_LEAN_EXTRA", "PDT_CTC_PAIR", "PDT_STEP_FLAT",
 )  # fmt: skip
 
 

@@ -680,6 +680,52 @@ def test_beam_search_advance_errors(device):
                               torch.ones(2, 3, dtype=torch.long, device=device))  # fmt: skip
 
 
+def test_host_report_left_armed_is_waited_for_before_it_is_armed_again(device, monkeypatch):
+    """The words in pinned host memory a kernel reports to: a launch whose report was never read -- an exception
+    between the launch and its wait, or inside the wait -- may still store to them, so arming them again first
+    synchronises the device; a report that was read is armed again without one.  Then beam_search_advance with
+    lengths reads its own verdict."""
+    from pydrobert_amd import _cabi
+
+    _cabi.host_report(device).disarm()  # (whatever an earlier test left)
+    syncs = []
+    sync = torch.cuda.synchronize
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda d=None: (syncs.append(d), sync(d))[1])
+    N, Kp, V, W, S = 4, 3, 6, 5, 4
+    reach = torch.full((N, Kp), S, dtype=torch.long, device=device)  # (a verdict of "y grows")
+    report = _cabi.host_report(device)
+    rc = _cabi.lib().pdt_lens_reach(_cabi.ptr(reach), Kp, 1, N, Kp, S, report.ptr, _cabi.stream_ptr(device))
+    assert rc == _cabi.PDT_OK and not syncs
+    report = _cabi.host_report(device)  # (armed again, its launch's report never read)
+    assert syncs == [device] and not report.words.any()
+    rc = _cabi.lib().pdt_lens_reach(_cabi.ptr(reach), Kp, 1, N, Kp, S, report.ptr, _cabi.stream_ptr(device))
+    assert rc == _cabi.PDT_OK
+
+    def interrupted():  # (as a KeyboardInterrupt would, without ending the session)
+        raise RuntimeError("interrupted")
+
+    with monkeypatch.context() as m:
+        m.setattr(_cabi.time, "perf_counter", interrupted)
+        with pytest.raises(RuntimeError, match="interrupted"):
+            report.wait()
+    report = _cabi.host_report(device)  # (armed again, its wait interrupted)
+    assert syncs == [device, device] and not report.words.any()
+    report.disarm()
+    rng = np.random.default_rng(78)
+    lpt = np.log(rng.dirichlet(np.ones(V), (N, Kp))).astype(np.float32)
+    lpp = rng.normal(size=(N, Kp)).astype(np.float32)
+    yp = rng.integers(0, V, (S, N, Kp))
+    ypl = rng.integers(0, S, (N, Kp))  # (no path as long as the history: y does not grow)
+    exp = oracle.beam_search_advance(lpt, W, lpp, yp, ypl)
+    tt = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+    act = [x.cpu().numpy() for x in F.beam_search_advance(tt(lpt), W, tt(lpp), tt(yp), tt(ypl))]
+    assert act[0].shape == exp[0].shape == (S, N, W)
+    assert np.array_equal(act[1], exp[1]) and np.array_equal(act[2], exp[2]) and np.array_equal(act[3], exp[3])
+    valid = np.arange(S)[:, None, None] < exp[1][None]
+    assert np.array_equal(np.where(valid, act[0], 0), np.where(valid, exp[0], 0))
+    assert syncs == [device, device]
+
+
 # ---------------------------------------------------------------------------------------
 # gradients of the decoding outputs (the reference keeps them in its autograd graph)
 # ---------------------------------------------------------------------------------------

@@ -95,7 +95,7 @@ shapes = {
                                      per_unit="utterance", cells=512 * 512),
     "lev_rowsync_kernel<false, false>": dict(what="optimal_completion masks, N=4096 T=512", units=4096, alg=8192 + 513 * 64,
                                              per_unit="utterance (tokens in, class bitmasks out)", cells=512 * 512),
-    "oc_expand_tiles_kernel": dict(what="optimal_completion expansion", units=4096, alg=8 * 513 * (C_oc or 0),
+    "oc_expand_": dict(what="optimal_completion expansion (any of its kernels)", units=4096, alg=8 * 513 * (C_oc or 0),
                                    per_unit="utterance ((H+1) x C int64 out)"),
     "ctc_search_kernel<1, 4, true": dict(what="fused CTC search N=4096 T=512 V=256 K=16 (+12 and +6 logits)", units=4096,
                                           alg=4 * 512 * 257 + 8 * 512 * 16 + 12 * 16, per_unit="utterance", frames=512),

@@ -624,6 +624,152 @@ __global__ void __launch_bounds__(NW * PDT_WAVE) oc_expand_tiles_kernel(const Oc
   }
 }
 
+// ---- phase 2, utterance-tile form over n (W <= 16) -------------------------------------------
+// The tiled form above reads every tile's tables once per chunk of h (nine times at the bench
+// shape, ~150 MB next to 2.08 GB of writes) and starts each chunk behind a barrier.  Here a
+// workgroup owns NB = 64 / Wp consecutive utterances for a range of h -- all of them unless the
+// grid would leave CUs idle -- loads their class-token tables into LDS once, and after that one
+// barrier its waves take the values of h in turn with nothing but the target stream in flight:
+//   * the run of one h (NB rows, NB * C * 8 contiguous bytes) has ONE bitmask word per lane
+//     (lane = (row, word)), fetched two values of h ahead into registers;
+//   * positions come from the wave scan as in the tiled form; each set bit writes its table index
+//     into a per-wave list at (row, position) -- no padding image is filled, since element (u, c)
+//     of the run is a token iff c < cnt_u, with cnt_u read from the row's last lane (ds_bpermute);
+//   * the way out has a fixed shape the compiler can count: per lane KB blocks of four pairs, every
+//     LDS read issued (padding elements read entry 0), 16-byte non-temporal stores.
+// It serves runs of at most 2 048 elements (KB <= 4) with C even, the operator's own case (C <= R);
+// everything else -- C > R or odd C from the C ABI, longer references -- goes to the tiled form.
+// Bench shape: 0.39 -> 0.34 ms, the fill rate of the box (EXPERIMENTS.md section 12.1).
+struct OcRunArgs {
+  const uint32_t *bitmask;
+  const int64_t *class_tokens;
+  int64_t *targets;
+  int64_t N, padding, tgt_sh;
+  int R, W, lgWp, Hout, C, NB, hchunk, ntiles;
+  int step_u, step_c;  // a lane's next pair: (128 / C, 128 % C) elements on
+};
+
+constexpr int kOcRunWaves = 8;
+constexpr int kOcRunMaxElems = 4 * 4 * 2 * PDT_WAVE;  // KB = 4 blocks of four 16-byte stores per lane
+
+__host__ __device__ inline size_t oc_run_lds(int R, int C, int NB) {
+  const size_t list = (((size_t)NB * C + 3) & ~(size_t)3) * 4;
+  return (size_t)NB * R * 8 + (size_t)kOcRunWaves * list;
+}
+
+template <int KB>
+__global__ void __launch_bounds__(kOcRunWaves * PDT_WAVE) oc_expand_runs_kernel(const OcRunArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int NW = kOcRunWaves;
+  constexpr int kThreads = NW * PDT_WAVE;
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  const int C = a.C, W = a.W, R = a.R, NB = a.NB, lgWp = a.lgWp;
+  const unsigned item = xcd_remap(blockIdx.x, gridDim.x);  // item = (h range, tile)
+  const int hc = (int)(item / (unsigned)a.ntiles);
+  const int tile = (int)(item - (unsigned)hc * (unsigned)a.ntiles);
+  const int64_t n_first = (int64_t)tile * NB;
+  const int rows = (int)min((int64_t)NB, a.N - n_first);
+  const int h_end = min(a.Hout, (hc + 1) * a.hchunk);
+  int64_t *ctok = reinterpret_cast<int64_t *>(smem);
+  int *list = reinterpret_cast<int *>(smem + (size_t)NB * R * 8) + (size_t)wave * (((size_t)NB * C + 3) & ~(size_t)3);
+  {  // the tile's tables: one contiguous block of class_tokens, eight loads in flight per thread
+    const int64_t *src = a.class_tokens + n_first * (int64_t)R;
+    const int total = rows * R;
+    for (int k0 = (int)threadIdx.x; k0 < total; k0 += kThreads * 8) {
+      int64_t v[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) v[q] = k0 + q * kThreads < total ? src[k0 + q * kThreads] : 0;
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (k0 + q * kThreads < total) ctok[k0 + q * kThreads] = v[q];
+    }
+  }
+  __syncthreads();  // the only one: from here on each wave runs alone
+  const int Wp = 1 << lgWp;
+  const int ur = lane >> lgWp, word = lane & (Wp - 1), seg = lane & ~(Wp - 1);
+  const bool live = ur < rows && word < W;
+  // every lane loads, from a clamped address, so that the loads are unconditional and the
+  // compiler counts them (a conditional load made it wait for all stores, vmcnt(0), every run)
+  const uint32_t *bm = a.bitmask + (n_first + min(ur, rows - 1)) * W + min(word, W - 1);
+  const int64_t bm_sh = a.N * W;
+  const int tab = ur * R + word * 32;
+  int *lrow = list + ur * C;
+  const int total = rows * C;
+  // the first element of this lane in the run, as (row, column)
+  const int e0 = 2 * lane;
+  const int u0 = e0 / C, c0 = e0 - u0 * C;
+  int h = hc * a.hchunk + wave;
+  const int h_last = h_end - 1;
+  unsigned w_next = bm[(int64_t)min(h, h_last) * bm_sh];
+  unsigned w_next2 = bm[(int64_t)min(h + NW, h_last) * bm_sh];
+  for (; h < h_end; h += NW) {
+    unsigned w = live ? w_next : 0u;
+    w_next = w_next2;
+    w_next2 = bm[(int64_t)min(h + 2 * NW, h_last) * bm_sh];
+    const int cnt = __popc(w);
+    const int incl = wave_incl_scan_add(cnt);
+    const int prev = __builtin_amdgcn_ds_bpermute((seg > 0 ? seg - 1 : 0) << 2, incl);
+    const int before = seg > 0 ? prev : 0;
+    const int row_cnt = incl - before;  // cnt_u at the row's last lane
+    // the word's classes into the list from both ends at once (a row's ~13 classes are neighbours,
+    // mostly in one or two words: half the serial iterations)
+    int lo = incl - cnt - before, hi = incl - 1 - before;
+    while (w) {
+      const int b0 = __builtin_ctz(w), b1 = 31 - __builtin_clz(w);
+      w &= ~((1u << b0) | (1u << b1));
+      lrow[lo++] = tab + b0;
+      lrow[hi--] = tab + b1;  // (b0 == b1: the same slot twice)
+    }
+    wave_sync();
+    int64_t *dst = a.targets + (int64_t)h * a.tgt_sh + n_first * C;
+    int u = u0, c = c0;
+    {
+      // 16-byte stores (C even: a pair never straddles two rows), 4 * KB per lane, a count the
+      // compiler sees; all LDS reads issued unconditionally, from index 0 for padding elements
+      typedef long long ll2 __attribute__((ext_vector_type(2)));
+      ll2 *d2 = reinterpret_cast<ll2 *>(dst);
+      const int2 *l2 = reinterpret_cast<const int2 *>(list);
+      const int pairs = total >> 1;
+#pragma unroll
+      for (int blk = 0; blk < KB; ++blk) {
+        int k[4], cc[4];
+        int2 id[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = (blk * 4 + q) * PDT_WAVE + lane;
+          k[q] = __builtin_amdgcn_ds_bpermute(((u << lgWp) + Wp - 1) << 2, row_cnt);
+          cc[q] = i < pairs ? c : C;
+          id[q] = l2[i < pairs ? i : 0];
+          u += a.step_u;
+          c += a.step_c;
+          if (c >= C) {
+            c -= C;
+            ++u;
+          }
+        }
+        ll2 v[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const bool vx = cc[q] < k[q], vy = cc[q] + 1 < k[q];
+          const int64_t tx = ctok[vx ? id[q].x : 0], ty = ctok[vy ? id[q].y : 0];
+          v[q].x = vx ? tx : a.padding;
+          v[q].y = vy ? ty : a.padding;
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = (blk * 4 + q) * PDT_WAVE + lane;
+          // (non-temporal: written once, never read back by this kernel)
+          if (i < pairs) __builtin_nontemporal_store(v[q], &d2[i]);
+        }
+      }
+    }
+    // (the next h's list writes may not overtake these reads: the LDS serves a wave's instructions
+    // in order, so only the compiler has to be told)
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 int launch_oc_expand(const uint32_t *bitmask, const int64_t *class_tokens, int R, int Hout,
                      int64_t N, int C, int64_t padding, int64_t *targets, int64_t tgt_sh,
                      int64_t tgt_sn, hipStream_t stream) {
@@ -631,6 +777,51 @@ int launch_oc_expand(const uint32_t *bitmask, const int64_t *class_tokens, int R
   if (W > PDT_WAVE) return PDT_E_TOO_LONG;
   // tiled form: rows that follow each other in memory (stride C along n or along h)
   const bool over_n = tgt_sn == C, over_h = tgt_sh == C;
+  // utterance-tile form: NB = 64 / Wp rows, one bitmask word per lane (4 at the bench shape),
+  // 16-byte stores (C even, runs on 16 bytes), a run of NB * C <= 2 048 elements
+  int lgWp = 0;
+  while ((1 << lgWp) < W) ++lgWp;
+  const int NB = PDT_WAVE >> lgWp;
+  const bool runs = over_n && W <= 16 && N < (1ll << 31) && (C & 1) == 0 && (tgt_sh & 1) == 0 &&
+                    (reinterpret_cast<uintptr_t>(targets) & 15) == 0 && (int64_t)NB * C <= kOcRunMaxElems;
+  if (runs) {
+    // LDS = NB tables (int64, <= 16 KiB) + one index list per wave (NB * C int32, <= 8 KiB): 31 KiB
+    // at the bench shape, so four workgroups of eight waves -- 32 waves, the most a CU holds -- fit
+    // on a CU (80 KiB at most: two).  The h range is split only when the tiles alone would leave
+    // CUs (256 on MI355X) with fewer than two workgroups -- below N = 2 048 at NB = 4; at the bench
+    // shape 1 024 tiles, one workgroup each, every table read once.
+    OcRunArgs a{};
+    a.bitmask = bitmask; a.class_tokens = class_tokens; a.targets = targets;
+    a.N = N; a.padding = padding; a.tgt_sh = tgt_sh; a.R = R; a.W = W; a.Hout = Hout; a.C = C;
+    a.lgWp = lgWp;
+    a.NB = NB;
+    const int64_t ntiles = (N + NB - 1) / NB;
+    const int nw = kOcRunWaves;
+    const int64_t want = 2 * 256;
+    int64_t hsplit = ntiles >= want ? 1 : (want + ntiles - 1) / ntiles;
+    hsplit = min(hsplit, (int64_t)((Hout + 2 * nw - 1) / (2 * nw)));  // >= two runs per wave
+    if (hsplit < 1) hsplit = 1;
+    a.hchunk = (int)((Hout + hsplit - 1) / hsplit);
+    hsplit = (Hout + a.hchunk - 1) / a.hchunk;
+    a.ntiles = (int)ntiles;
+    const int pairs = NB * C / 2;
+    const int KB = pairs <= 4 * PDT_WAVE ? 1 : pairs <= 8 * PDT_WAVE ? 2 : 4;
+    a.step_u = 2 * PDT_WAVE / C;
+    a.step_c = 2 * PDT_WAVE % C;
+    const int64_t grid = ntiles * hsplit;
+    if (grid < (1ll << 31)) {
+      const size_t smem = oc_run_lds(R, C, NB);
+      const auto kern = KB == 1 ? oc_expand_runs_kernel<1> : KB == 2 ? oc_expand_runs_kernel<2>
+                                                                     : oc_expand_runs_kernel<4>;
+      if (smem > 64 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        if (e != hipSuccess) return (int)e;
+      }
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(nw * PDT_WAVE), smem, stream, a);
+      return (int)hipGetLastError();
+    }
+  }
   if ((over_n || over_h) && N < (1ll << 31)) {
     OcTileArgs a{};
     a.bitmask = bitmask; a.class_tokens = class_tokens; a.targets = targets;

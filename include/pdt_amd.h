@@ -695,6 +695,46 @@ int pdt_mvn_apply(const void *x, int dtype, int64_t A, int64_t X, int64_t B, con
 int pdt_mvn_backward(const void *grad_y, const void *x, int dtype, int64_t A, int64_t X, int64_t B, const void *mean,
                      const void *coef, void *grad_x, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Soft attention (reference _attn.py:200-223): out[r] = sum_t a[r, t] value[r, t], a the softmax
+ * over t of the scores with masked frames at -inf; lse[r] its log-sum-exp.  dtype 0 float32,
+ * 1 float64 (accumulated in the same type).
+ * desc: PDT_ATTN_DESC_LEN int64, read on the host and copied into the kernel arguments:
+ *   [0] nd <= PDT_ATTN_MAX_DIMS row dims, [1] R rows = product of the sizes = G * M, [2] G groups,
+ *   [3] M rows per group (the innermost row dims, over which key, value and their gradients are
+ *   broadcast), [4] T, [5] D (0 in the pool forms), [6] Dv, [7 .. 7 + MAX) the row sizes (outermost
+ *   first), then per operand slot (query or score, key, value, mask, out / grad_out, grad_query or
+ *   grad_score, grad_key, grad_value) MAX row strides, the T stride and the feature stride, in
+ *   elements; 0 broadcasts.  lse is (R,) in row order.  mask is bool bytes or NULL (all kept).
+ * pdt_attn_dot: scores *scale * query . key (scale: one double in host memory).  pdt_attn_pool: the scores given (score slot).
+ * pdt_attn_*_backward: the gradients, recomputing a from lse; grad_key / grad_value are summed
+ * over the group.  Masked frames contribute exactly 0.  No float atomics: bitwise reproducible.
+ * Workspaces of pdt_attn_workspace_bytes(desc, dtype, kind) bytes (kind 0 dot, 1 dot backward,
+ * 2 pool, 3 pool backward; -1 for a bad descriptor).  R == 0 is OK; T == 0 with rows is an error
+ * (the caller returns zeros).
+ * ------------------------------------------------------------------------------------- */
+#define PDT_ATTN_MAX_DIMS 8
+#define PDT_ATTN_SLOTS 8
+#define PDT_ATTN_DESC_LEN (7 + PDT_ATTN_MAX_DIMS + PDT_ATTN_SLOTS * (PDT_ATTN_MAX_DIMS + 2))
+
+int64_t pdt_attn_workspace_bytes(const int64_t *desc, int dtype, int kind);
+
+int pdt_attn_dot(const int64_t *desc, int dtype, const void *query, const void *key, const void *value,
+                 const void *mask, const double *scale, void *out, void *lse, void *workspace, int64_t workspace_bytes,
+                 void *stream);
+
+int pdt_attn_dot_backward(const int64_t *desc, int dtype, const void *query, const void *key, const void *value,
+                          const void *mask, const double *scale, const void *out, const void *lse, const void *grad_out,
+                          void *grad_query, void *grad_key, void *grad_value, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+
+int pdt_attn_pool(const int64_t *desc, int dtype, const void *score, const void *value, const void *mask, void *out,
+                  void *lse, void *workspace, int64_t workspace_bytes, void *stream);
+
+int pdt_attn_pool_backward(const int64_t *desc, int dtype, const void *score, const void *value, const void *mask,
+                           const void *out, const void *lse, const void *grad_out, void *grad_score,
+                           void *grad_value, void *workspace, int64_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -115,6 +115,8 @@ extern "C" {
 //     then, additively (no existing entry point changed): pdt_feat_deltas, pdt_feat_deltas_backward,
 //     pdt_mvn_stats_workspace_bytes, pdt_mvn_stats, pdt_mvn_apply, pdt_mvn_backward
 //     and, with no entry point changed, the switch PDT_WALK_TABLE moved to the host package (no native code read it)
+//     then, additively: pdt_attn_dot, pdt_attn_dot_backward, pdt_attn_pool, pdt_attn_pool_backward,
+//     pdt_attn_workspace_bytes
 int pdt_amd_abi_version(void) { return 12; }
 
 int pdt_amd_set_switch(const char *name, int value) {

@@ -187,6 +187,13 @@ SIGNATURES = {
     "pdt_mvn_stats": (_INT, [_P, _P, _P, _INT, _I64, _I64, _I64, _INT, _P, _P, _P, _P, _I64, _P]),
     "pdt_mvn_apply": (_INT, [_P, _INT, _I64, _I64, _I64, _P, _P, _P, _P]),
     "pdt_mvn_backward": (_INT, [_P, _P, _INT, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "pdt_attn_workspace_bytes": (_I64, [_P, _INT, _INT]),
+    "pdt_attn_dot": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_attn_dot_backward": (
+        _INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
+    ),
+    "pdt_attn_pool": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_attn_pool_backward": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_ctc_prefix_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "pdt_ctc_prefix_search_plan": (_INT, [_I64, _I64, _P]),
     "pdt_ctc_prefix_search": (

@@ -1,6 +1,13 @@
 """Module namespace -- mirrors ``pydrobert.torch.modules`` (modules.py:28-124) for the
 operators on the MI355X hot path."""
 
+from ._attn import (
+    ConcatSoftAttention,
+    DotProductSoftAttention,
+    GeneralizedDotProductSoftAttention,
+    GlobalSoftAttention,
+    MultiHeadedAttention,
+)
 from ._decoding import BeamSearch, CTCPrefixSearch
 from ._img import (
     DenseImageWarp,
@@ -34,6 +41,11 @@ from ._string import (
 )
 
 __all__ = [
+    "ConcatSoftAttention",
+    "DotProductSoftAttention",
+    "GeneralizedDotProductSoftAttention",
+    "GlobalSoftAttention",
+    "MultiHeadedAttention",
     "FeatureDeltas",
     "MeanVarianceNormalization",
     "PadVariable",

@@ -735,6 +735,77 @@ int pdt_attn_pool_backward(const int64_t *desc, int dtype, const void *score, co
                            const void *out, const void *lse, const void *grad_out, void *grad_score,
                            void *grad_value, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Slicing and chunking (reference _pad.py:257-548, _feats.py:417-930) on two primitives: stable
+ * compaction within a row (one workgroup per row; ranks by wave ballot + popcount with a carry)
+ * and a copy with an index map and a padding rule.  All lengths, slices and counts are int64;
+ * maps are int32.  Every output element is written once: no pre-fill, no atomics.
+ * pdt_compact_mask: mask bool bytes at mask[n * m_sn + t * m_st]; src[n, j] = the step of the j-th
+ *   kept one (-1 for j >= counts[n]), rank[n, t] = where step t goes (-1 if dropped), both at
+ *   [n * o_sn + . * o_st]; either may be NULL.
+ * pdt_gather_steps: out[n, t, :] = x[n, map[n, t], :] (x through the element strides x_sn / x_st,
+ *   F contiguous; map through m_sn / m_st), *fill where the map is negative; out (N, To, F), or
+ *   (To, N, F) when time_major.  Elements of elem_bytes in {1, 2, 4, 8, 16} move as opaque words
+ *   (16: a caller whose F elements, strides and pointers are multiples of 16 bytes passes groups
+ *   of elements as one word, with F, the strides and *fill in those units; also pdt_chunk_by_slices).
+ * pdt_chunk_by_slices: out[n, t, :], t < Tp, reads step s = slices[n, 0] + t of x[n] for
+ *   t < slices[n, 1] - slices[n, 0]; with len = lens[n] (NULL: T), 0 <= s < len is x[n, s]; outside,
+ *   mode 0 is *fill, 1 reflect (x[n, -s], x[n, 2 (len - 1) - s]), 2 replicate (x[n, clamp(s)]);
+ *   the other steps are *fill.  The caller checks what reflect / replicate require.
+ * pdt_chunk_stats: what the caller reads back first, in one launch: chunk_lens[n] =
+ *   max(end - start, 0) and stats[0] = T' (the largest left pad, chunk length or right pad, pads of
+ *   empty slices counting 0), stats[1] = max(pad - len) over both pads (>= 0: reflect is refused),
+ *   stats[2] = min len (< 1: replicate is refused).  A len beyond T counts as T in the two copies.
+ * pdt_chunk_by_slices_backward: the adjoint as a gather, dtype 0 float32 / 1 float64;
+ *   grad_out (N, Tp, F), grad_x (N, T, F) contiguous.
+ * pdt_chunk_tokens: refs (N, R, 3), slices (N, 2), ref_lens (N,) or NULL; out (N, R, 3) holds the
+ *   kept triples left-packed (boundaries + slices[n, 0] unless retain), zeros past counts[n].
+ * pdt_slice_*: the (slices, sources) lists of slice_spect_data.  With emit == 0 only counts[n]
+ *   (kept candidates per row) is written; with emit != 0 row n's slices go to base[n] + rank
+ *   (base NULL: n * TT, pdt_slice_fixed without lengths).  fixed: candidate k < TT is
+ *   [a0 + k shift, a0 + k shift + width), kept when in_lens[n] > m0 + k shift.  ref: input
+ *   (N, T, 3); other_lens NULL means the end of the row's last triple.  ali: input (N, T) labels;
+ *   pdt_slice_ali_segments writes the first step of each run of equal labels (seg (N, T) int32,
+ *   counts = runs per row), pdt_slice_ali_emit slice k < cnt[n] of row n from them: valid_only
+ *   (seg[k], end of run k + left + right), else (seg[max(k - left, 0)], end of run
+ *   min(k + right, runs - 1)); the last run ends at min(in_lens[n], T).
+ * ------------------------------------------------------------------------------------- */
+int pdt_compact_mask(const void *mask, int64_t N, int64_t T, int64_t m_sn, int64_t m_st, int32_t *src,
+                     int32_t *rank, int64_t o_sn, int64_t o_st, int64_t *counts, void *stream);
+
+int pdt_gather_steps(const void *x, int64_t N, int64_t T, int64_t F, int64_t elem_bytes, int64_t x_sn,
+                     int64_t x_st, const int32_t *map, int64_t m_sn, int64_t m_st, int64_t To,
+                     int time_major, const void *fill, void *out, void *stream);
+
+int pdt_chunk_by_slices(const void *x, int64_t N, int64_t T, int64_t F, int64_t elem_bytes, int64_t x_sn,
+                        int64_t x_st, const int64_t *slices, const int64_t *lens, int mode,
+                        const void *fill, int64_t Tp, void *out, void *stream);
+
+int pdt_chunk_stats(const int64_t *slices, const int64_t *lens, int64_t N, int64_t T, int64_t *chunk_lens,
+                    int64_t *stats, void *stream);
+
+int pdt_chunk_by_slices_backward(const void *grad_out, int dtype, int64_t N, int64_t T, int64_t F,
+                                 const int64_t *slices, const int64_t *lens, int mode, int64_t Tp,
+                                 void *grad_x, void *stream);
+
+int pdt_chunk_tokens(const int64_t *refs, int64_t N, int64_t R, const int64_t *slices, const int64_t *ref_lens,
+                     int partial, int retain, int64_t *out, int64_t *counts, void *stream);
+
+int pdt_slice_fixed(int64_t N, int64_t TT, const int64_t *in_lens, int64_t a0, int64_t shift, int64_t width,
+                    int64_t m0, const int64_t *base, int emit, int64_t *slices, int64_t *sources,
+                    int64_t *counts, void *stream);
+
+int pdt_slice_ref(const int64_t *input, int64_t N, int64_t T, const int64_t *in_lens, const int64_t *other_lens,
+                  int64_t left, int64_t right, int valid_only, const int64_t *base, int emit, int64_t *slices,
+                  int64_t *sources, int64_t *counts, void *stream);
+
+int pdt_slice_ali_segments(const int64_t *input, int64_t N, int64_t T, const int64_t *in_lens, int32_t *seg,
+                           int64_t *counts, void *stream);
+
+int pdt_slice_ali_emit(const int32_t *seg, int64_t N, int64_t T, const int64_t *in_lens, const int64_t *nseg,
+                       const int64_t *cnt, const int64_t *base, int64_t left, int64_t right, int valid_only,
+                       int64_t *slices, int64_t *sources, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

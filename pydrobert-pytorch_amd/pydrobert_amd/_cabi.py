@@ -194,6 +194,16 @@ SIGNATURES = {
     ),
     "pdt_attn_pool": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_attn_pool_backward": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_compact_mask": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
+    "pdt_gather_steps": (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _INT, _P, _P, _P]),
+    "pdt_chunk_by_slices": (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _INT, _P, _I64, _P, _P]),
+    "pdt_chunk_stats": (_INT, [_P, _P, _I64, _I64, _P, _P, _P]),
+    "pdt_chunk_by_slices_backward": (_INT, [_P, _INT, _I64, _I64, _I64, _P, _P, _INT, _I64, _P, _P]),
+    "pdt_chunk_tokens": (_INT, [_P, _I64, _I64, _P, _P, _INT, _INT, _P, _P, _P]),
+    "pdt_slice_fixed": (_INT, [_I64, _I64, _P, _I64, _I64, _I64, _I64, _P, _INT, _P, _P, _P, _P]),
+    "pdt_slice_ref": (_INT, [_P, _I64, _I64, _P, _P, _I64, _I64, _INT, _P, _INT, _P, _P, _P, _P]),
+    "pdt_slice_ali_segments": (_INT, [_P, _I64, _I64, _P, _P, _P, _P]),
+    "pdt_slice_ali_emit": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _INT, _P, _P, _P]),
     "pdt_ctc_prefix_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "pdt_ctc_prefix_search_plan": (_INT, [_I64, _I64, _P]),
     "pdt_ctc_prefix_search": (

@@ -5,6 +5,9 @@ On a ROCm device every pass is HIP (``csrc/feats.hip``): the deltas in one pass 
 layout, the statistics as a fixed-order float64 reduction, the normalisation and both backward passes
 elementwise.  No host read in any forward, backward or ``accumulate``.  CPU tensors (data-loader
 workers) take a torch body written from the same formulas.
+
+``slice_spect_data`` and ``chunk_token_sequences_by_slices`` (reference _feats.py:417-930) run on the row
+compaction of ``csrc/seq_chunk.hip``, with the same split between HIP and the torch body.
 """
 from typing import List, Optional, Tuple
 
@@ -13,7 +16,16 @@ from torch.library import custom_op, register_autograd
 
 from . import _cabi, argcheck, config
 
-__all__ = ["FeatureDeltas", "MeanVarianceNormalization", "feat_deltas", "mean_var_norm"]
+__all__ = [
+    "ChunkTokenSequencesBySlices",
+    "FeatureDeltas",
+    "MeanVarianceNormalization",
+    "SliceSpectData",
+    "chunk_token_sequences_by_slices",
+    "feat_deltas",
+    "mean_var_norm",
+    "slice_spect_data",
+]
 
 _DTYPES = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}
 _PAD_MODES = {"replicate": 0, "reflect": 1, "circular": 2, "constant": 3}
@@ -660,3 +672,362 @@ class MeanVarianceNormalization(torch.nn.Module):
             self.sum = None
             self.sumsq = None
             self.count = None
+
+
+# ----------------------------------------------------------------------------------------------------------
+# slices of spectral data and of token sequences (csrc/seq_chunk.hip)
+
+_POLICIES = ("fixed", "ali", "ref")
+_WINDOW_TYPES = ("symmetric", "causal", "future")
+
+
+def _fixed_geometry(T: int, window_type: str, valid_only: bool, lobe_size: int) -> Tuple[int, int, int, int, int]:
+    """(TT, a0, shift, width, m0) of policy 'fixed' (reference _feats.py:459-484): candidate k < TT is
+    [a0 + k shift, a0 + k shift + width) and counts for a row whose length exceeds m0 + k shift."""
+    shift = lobe_size + 1
+    if window_type == "symmetric":
+        width = 2 * lobe_size + 1
+        if valid_only:
+            return -(-max(T - width + 1, 0) // shift), 0, shift, width, width - 1
+        half = shift // 2
+        return (T + half) // shift, half - lobe_size, shift, width, half
+    if valid_only:
+        return -(-max(T - lobe_size, 0) // shift), 0, shift, shift, shift - 1
+    if window_type == "causal":
+        return -(-T // shift), -lobe_size, shift, shift, 0
+    return -(-T // shift), 0, shift, shift, 0
+
+
+def _lobes(window_type: str, lobe_size: int) -> Tuple[int, int]:
+    left = lobe_size if window_type in ("symmetric", "causal") else 0
+    right = lobe_size if window_type in ("symmetric", "future") else 0
+    return left, right
+
+
+def _slice_checks(input, in_lens, other_lens, policy, window_type, lobe_size):
+    N = input.shape[0]
+    if lobe_size < 0:
+        raise RuntimeError("Expected non-negative lobe_size, got {}".format(lobe_size))
+    if window_type not in _WINDOW_TYPES:
+        raise RuntimeError(
+            "expected window_type to be one of 'symmetric', 'casual', or 'future' got '{}'".format(window_type)
+        )
+    if policy not in _POLICIES:
+        raise RuntimeError("Expected policy to be one of 'fixed', 'ali', or 'ref'; got '{}'".format(policy))
+    if policy == "ali" and input.dim() != 2:
+        raise RuntimeError("expected tensor of dimension 2 with policy 'ali'")
+    if policy == "ref":
+        if input.dim() != 3:
+            raise RuntimeError("Expected input to be 3-dimensional, got {}".format(input.dim()))
+        if input.shape[2] != 3:
+            raise RuntimeError("Expected 3rd dimension of input to be of size 3, got {}".format(input.shape[2]))
+        if other_lens is not None and tuple(other_lens.shape) != (N,):
+            raise RuntimeError("Expected other_lens to have shape ({},); got {}".format(N, tuple(other_lens.shape)))
+    if in_lens is not None and tuple(in_lens.shape) != (N,):
+        raise RuntimeError("Expected in_lens to be of shape ({},); got {}".format(N, tuple(in_lens.shape)))
+
+
+def _labels(x: torch.Tensor) -> torch.Tensor:
+    """Alignment labels as contiguous int64 that are equal exactly where the labels are."""
+    if x.is_floating_point():
+        x = (x.double() + 0.0).view(torch.int64)  # (-0.0 + 0.0 is +0.0: equal values, equal bits)
+    return x.long().contiguous()
+
+
+def _slice_spect_torch(input, in_lens, other_lens, policy, window_type, valid_only, lobe_size):
+    """Torch body (CPU tensors, and the device restatement the timing tool compares with)."""
+    N, T = input.shape[0], input.shape[1]
+    device = input.device
+    rows = torch.arange(N, device=device)
+    left, right = _lobes(window_type, lobe_size)
+    if policy == "fixed":
+        TT, a0, shift, width, m0 = _fixed_geometry(T, window_type, valid_only, lobe_size)
+        k = torch.arange(TT, device=device) * shift
+        slices = torch.stack([a0 + k, a0 + k + width], 1).expand(N, TT, 2).flatten(0, 1)
+        sources = rows.view(N, 1).expand(N, TT).flatten()
+        if in_lens is not None:
+            keep = (in_lens.view(N, 1) > m0 + k).flatten()
+            slices, sources = slices[keep], sources[keep]
+        return slices.contiguous(), sources.contiguous()
+    lens = torch.full((N,), T, device=device) if in_lens is None else in_lens.long().clamp_max(T)
+    steps = torch.arange(T, device=device)
+    if policy == "ref":
+        starts, ends = input[..., 1].long(), input[..., 2].long()
+        if other_lens is None:  # the end of the row's last triple
+            other_lens = ends[rows, (lens - 1).clamp_min(0)].masked_fill(lens == 0, 0)
+        keep = (lens.view(N, 1) > steps) & (starts >= 0) & (ends >= 0)
+        starts, ends, other = starts - left, ends + right, other_lens.view(N, 1)
+        keep = keep & ((starts >= 0) & (ends <= other) if valid_only else (ends > 0) & (starts < other))
+        keep = keep & (starts < ends)
+        return torch.stack([starts[keep], ends[keep]], 1), rows.view(N, 1).expand(N, T)[keep]
+    # ali: runs of equal labels within the row's length, then the closed form of the reference's lobe loop
+    x = _labels(input)
+    first = torch.cat([torch.ones((N, 1), dtype=torch.bool, device=device), x[:, 1:] != x[:, :-1]], 1)
+    first = first & (steps < lens.view(N, 1))
+    K = first.sum(1)
+    where = first.nonzero()
+    src, st = where[:, 0], where[:, 1]
+    NN = src.numel()
+    base = K.cumsum(0) - K
+    k = torch.arange(NN, device=device) - base[src]
+    last_of_row = k == K[src] - 1
+    en = torch.where(last_of_row, lens[src], torch.cat([st[1:], st.new_zeros(1)]))
+    if valid_only:
+        keep = k + left + right < K[src]
+        i = torch.arange(NN, device=device)[keep]
+        return torch.stack([st[i], en[i + left + right]], 1), src[keep]
+    lo = base[src] + (k - left).clamp_min(0)
+    hi = base[src] + torch.minimum(k + right, K[src] - 1)
+    return torch.stack([st[lo], en[hi]], 1), src
+
+
+def _row_offsets(counts: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """(exclusive scan of the row counts, their total): the one host read of a flat list's size."""
+    ends = counts.cumsum(0)
+    return (ends - counts).contiguous(), int(ends[-1].item())
+
+
+def _slice_spect_hip(input, in_lens, other_lens, policy, window_type, valid_only, lobe_size):
+    device = _cabi.require_hip(input, in_lens, other_lens)
+    N, T = input.shape[0], input.shape[1]
+    lib = _cabi.lib()
+    left, right = _lobes(window_type, lobe_size)
+    ln = None if in_lens is None else in_lens.long().contiguous()
+
+    def empty(n):
+        return (torch.empty((n, 2), dtype=torch.long, device=device), torch.empty((n,), dtype=torch.long, device=device))
+
+    with _cabi.on_device(device):
+        stream = _cabi.stream_ptr(device)
+        counts = torch.zeros((N,), dtype=torch.long, device=device)
+        if policy == "fixed":
+            TT, a0, shift, width, m0 = _fixed_geometry(T, window_type, valid_only, lobe_size)
+            if N * TT == 0:
+                return empty(0)
+
+            def run(base, emit, slices, sources):
+                rc = lib.pdt_slice_fixed(N, TT, _cabi.ptr(ln), a0, shift, width, m0, _cabi.ptr(base), emit,
+                                         _cabi.ptr(slices), _cabi.ptr(sources), _cabi.ptr(counts), stream)  # fmt: skip
+                _cabi.check(rc, "pdt_slice_fixed")
+
+            if ln is None:  # every candidate counts: the size is known, no host read
+                slices, sources = empty(N * TT)
+                run(None, 1, slices, sources)
+                return slices, sources
+        elif policy == "ref":
+            if N == 0:
+                return empty(0)
+            x = input.long().contiguous()
+            ol = None if other_lens is None else other_lens.long().contiguous()
+
+            def run(base, emit, slices, sources):
+                rc = lib.pdt_slice_ref(_cabi.ptr(x), N, T, _cabi.ptr(ln), _cabi.ptr(ol), left, right, int(valid_only),
+                                       _cabi.ptr(base), emit, _cabi.ptr(slices), _cabi.ptr(sources), _cabi.ptr(counts),
+                                       stream)  # fmt: skip
+                _cabi.check(rc, "pdt_slice_ref")
+
+        else:
+            if N == 0:
+                return empty(0)
+            x = _labels(input)
+            seg = torch.empty((N, T), dtype=torch.int32, device=device)
+            rc = lib.pdt_slice_ali_segments(_cabi.ptr(x), N, T, _cabi.ptr(ln), _cabi.ptr(seg), _cabi.ptr(counts), stream)
+            _cabi.check(rc, "pdt_slice_ali_segments")
+            cnt = (counts - (left + right)).clamp_min(0) if valid_only else counts
+            base, total = _row_offsets(cnt)
+            slices, sources = empty(total)
+            if total:
+                rc = lib.pdt_slice_ali_emit(_cabi.ptr(seg), N, T, _cabi.ptr(ln), _cabi.ptr(counts), _cabi.ptr(cnt),
+                                            _cabi.ptr(base), left, right, int(valid_only), _cabi.ptr(slices),
+                                            _cabi.ptr(sources), stream)  # fmt: skip
+                _cabi.check(rc, "pdt_slice_ali_emit")
+            return slices, sources
+        # a run that counts, the one host read, a run that writes each row at its offset
+        run(None, 0, None, None)
+        base, total = _row_offsets(counts)
+        slices, sources = empty(total)
+        if total:
+            run(base, 1, slices, sources)
+        return slices, sources
+
+
+@custom_op("pydrobert_amd::slice_spect_data", mutates_args=())
+def _slice_spect_data_op(
+    input: torch.Tensor, in_lens: Optional[torch.Tensor], other_lens: Optional[torch.Tensor], policy: str,
+    window_type: str, valid_only: bool, lobe_size: int,
+) -> Tuple[torch.Tensor, torch.Tensor]:  # fmt: skip
+    if input.dim() < 2:
+        raise RuntimeError("Expected input to be at least 2-dimensional; got {}".format(input.dim()))
+    if not input.shape[1]:
+        return (torch.empty((0, 2), dtype=torch.long, device=input.device),
+                torch.empty((0,), dtype=torch.long, device=input.device))  # fmt: skip
+    _slice_checks(input, in_lens, other_lens, policy, window_type, lobe_size)
+    args = (input.detach(), None if in_lens is None else in_lens.detach(),
+            None if other_lens is None else other_lens.detach(), policy, window_type, valid_only, lobe_size)  # fmt: skip
+    if input.device.type == "cpu":
+        return _slice_spect_torch(*args)
+    return _slice_spect_hip(*args)
+
+
+@_slice_spect_data_op.register_fake
+def _(input, in_lens, other_lens, policy, window_type, valid_only, lobe_size):
+    n = torch.library.get_ctx().new_dynamic_size()
+    return input.new_empty((n, 2), dtype=torch.long), input.new_empty((n,), dtype=torch.long)
+
+
+def slice_spect_data(
+    input: torch.Tensor,
+    in_lens: Optional[torch.Tensor] = None,
+    other_lens: Optional[torch.Tensor] = None,
+    policy: str = "fixed",
+    window_type: str = "symmetric",
+    valid_only: bool = True,
+    lobe_size: int = 0,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Functional version of :class:`SliceSpectData` (reference _feats.py:430-588)."""
+    if not torch.jit.is_scripting():
+        if not torch.jit.is_tracing() and _cabi.plain_call(input, in_lens, other_lens):
+            return _slice_spect_data_op._init_fn(input, in_lens, other_lens, policy, window_type, valid_only, lobe_size)
+    return torch.ops.pydrobert_amd.slice_spect_data(
+        input, in_lens, other_lens, policy, window_type, valid_only, lobe_size
+    )
+
+
+class SliceSpectData(torch.nn.Module):
+    """Determine slices of feature chunks by policy ``fixed`` (windows of fixed size and shift), ``ali``
+    (runs of equal alignment labels) or ``ref`` (segments of token triples), each widened by ``lobe_size``
+    according to ``window_type`` (reference _feats.py:591-787).  Returns ``(slices, sources)``: ``(M, 2)``
+    start / end pairs and the batch row each came from, rows in order."""
+
+    __constants__ = ("policy", "window_type", "valid_only", "lobe_size")
+    policy: str
+    window_type: str
+    valid_only: bool
+    lobe_size: int
+
+    def __init__(
+        self,
+        policy: str = "fixed",
+        window_type: str = "symmetric",
+        valid_only: bool = True,
+        lobe_size: int = 0,
+    ) -> None:
+        policy = argcheck.is_in(policy, _POLICIES, "policy")
+        window_type = argcheck.is_in(window_type, _WINDOW_TYPES, "window_type")
+        valid_only = argcheck.is_bool(valid_only, "valid_only")
+        lobe_size = argcheck.is_nonnegi(lobe_size, "lobe_size")
+        super().__init__()
+        self.policy, self.window_type, self.lobe_size = policy, window_type, lobe_size
+        self.valid_only = valid_only
+
+    def extra_repr(self) -> str:
+        return "policy={}, window_type={}, lobe_size={}, valid_only={}".format(
+            self.policy, self.window_type, self.lobe_size, self.valid_only
+        )
+
+    def forward(
+        self,
+        input: torch.Tensor,
+        in_lens: Optional[torch.Tensor] = None,
+        other_lens: Optional[torch.Tensor] = None,
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        return slice_spect_data(
+            input, in_lens, other_lens, self.policy, self.window_type, self.valid_only, self.lobe_size
+        )
+
+
+def _chunk_tokens_torch(refs, slices, ref_lens, partial, retain):
+    N, R = refs.shape[0], refs.shape[1]
+    steps = torch.arange(R, device=refs.device)
+    rs, re, ss, se = refs[..., 1], refs[..., 2], slices[:, 0:1], slices[:, 1:2]
+    keep = (rs >= 0) & (re >= 0) & (re >= rs)
+    if ref_lens is not None:
+        keep = keep & (ref_lens.unsqueeze(1) > steps)
+    keep = keep & ((ss < re) & (se > rs) if partial else (ss <= rs) & (se >= re))
+    lens = keep.long().sum(1)
+    order = torch.argsort((~keep).to(torch.uint8), dim=1, stable=True)
+    out = refs.gather(1, order.unsqueeze(2).expand(N, R, 3))
+    if not retain:  # (the reference adds the slice start, _feats.py:836)
+        out = torch.cat([out[..., :1], out[..., 1:] + slices[:, 0].view(N, 1, 1)], 2)
+    return out.masked_fill((steps >= lens.unsqueeze(1)).unsqueeze(2), 0), lens
+
+
+@custom_op("pydrobert_amd::chunk_token_sequences_by_slices", mutates_args=())
+def _chunk_tokens_op(
+    refs: torch.Tensor, slices: torch.Tensor, ref_lens: Optional[torch.Tensor], partial: bool, retain: bool
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    if refs.dim() == 2:
+        return refs.new_empty((0, refs.shape[1])), slices.new_empty((0,))
+    if refs.dim() != 3 or refs.shape[2] != 3:
+        raise RuntimeError(
+            "Expected refs to be 2-dimensional or 3-dimensional with final dimension size 3. "
+            "Got shape '{}'".format(tuple(refs.shape))
+        )
+    N, R = refs.shape[0], refs.shape[1]
+    if tuple(slices.shape) != (N, 2):
+        raise RuntimeError("Expected slices to be a tensor of shape ({}, 2), got {}".format(N, tuple(slices.shape)))
+    if ref_lens is not None and tuple(ref_lens.shape) != (N,):
+        raise RuntimeError("Expected ref_lens to be a tensor of shape ({},), got {}".format(N, tuple(ref_lens.shape)))
+    if refs.is_floating_point() or refs.dtype == torch.bool:
+        raise RuntimeError("Expected refs to be an integer tensor, got {}".format(refs.dtype))
+    if refs.device.type == "cpu":
+        out, lens = _chunk_tokens_torch(refs.detach(), slices.detach().to(refs.dtype), ref_lens, partial, retain)
+        return out.contiguous(), lens
+    device = _cabi.require_hip(refs, slices, ref_lens)
+    rf = refs.detach().long().contiguous()
+    sl = slices.detach().long().contiguous()
+    rl = None if ref_lens is None else ref_lens.detach().long().contiguous()
+    out = torch.empty((N, R, 3), dtype=torch.long, device=device)
+    lens = torch.zeros((N,), dtype=torch.long, device=device)
+    with _cabi.on_device(device):
+        rc = _cabi.lib().pdt_chunk_tokens(
+            _cabi.ptr(rf) if R else None, N, R, _cabi.ptr(sl), _cabi.ptr(rl), int(partial), int(retain),
+            _cabi.ptr(out) if R else None, _cabi.ptr(lens), _cabi.stream_ptr(device),
+        )  # fmt: skip
+    _cabi.check(rc, "pdt_chunk_tokens")
+    return out.to(refs.dtype), lens
+
+
+@_chunk_tokens_op.register_fake
+def _(refs, slices, ref_lens, partial, retain):
+    if refs.dim() == 2:
+        return refs.new_empty((0, refs.shape[1])), slices.new_empty((0,))
+    return refs.new_empty(refs.shape), slices.new_empty((refs.shape[0],), dtype=torch.long)
+
+
+def chunk_token_sequences_by_slices(
+    refs: torch.Tensor,
+    slices: torch.Tensor,
+    ref_lens: Optional[torch.Tensor] = None,
+    partial: bool = False,
+    retain: bool = False,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Functional version of :class:`ChunkTokenSequencesBySlices` (reference _feats.py:790-837)."""
+    if not torch.jit.is_scripting():
+        if not torch.jit.is_tracing() and _cabi.plain_call(refs, slices, ref_lens):
+            return _chunk_tokens_op._init_fn(refs, slices, ref_lens, partial, retain)
+    return torch.ops.pydrobert_amd.chunk_token_sequences_by_slices(refs, slices, ref_lens, partial, retain)
+
+
+class ChunkTokenSequencesBySlices(torch.nn.Module):
+    """Keep the ``(tok, start, end)`` triples of each row that fall in the row's slice -- within it, or with
+    ``partial`` overlapping it -- left-packed (reference _feats.py:840-930).  Returns ``(chunked,
+    chunked_lens)``; triples at or beyond ``chunked_lens[n]`` are zeros."""
+
+    __constants__ = ("partial", "retain")
+    partial: bool
+    retain: bool
+
+    def __init__(self, partial: bool = False, retain: bool = False) -> None:
+        partial = argcheck.is_bool(partial, "partial")
+        retain = argcheck.is_bool(retain, "retain")
+        super().__init__()
+        self.partial, self.retain = partial, retain
+
+    def extra_repr(self) -> str:
+        return ", ".join(name for name in ("partial", "retain") if getattr(self, name))
+
+    def forward(
+        self, ref: torch.Tensor, slices: torch.Tensor, ref_lens: Optional[torch.Tensor] = None
+    ) -> Tuple[torch.Tensor, torch.Tensor]:
+        return chunk_token_sequences_by_slices(ref, slices, ref_lens, self.partial, self.retain)

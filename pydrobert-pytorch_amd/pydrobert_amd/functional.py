@@ -17,8 +17,8 @@ from ._img import (
     spec_augment_draw_parameters,
     warp_1d_grid,
 )
-from ._feats import feat_deltas, mean_var_norm
-from ._pad import pad_variable
+from ._feats import chunk_token_sequences_by_slices, feat_deltas, mean_var_norm, slice_spect_data
+from ._pad import chunk_by_slices, pad_masked_sequence, pad_variable
 from ._string import (
     hard_optimal_completion_distillation_loss,
     minimum_error_rate_loss,
@@ -31,6 +31,10 @@ from ._string import (
 )
 
 __all__ = [
+    "chunk_by_slices",
+    "chunk_token_sequences_by_slices",
+    "pad_masked_sequence",
+    "slice_spect_data",
     "feat_deltas",
     "mean_var_norm",
     "pad_variable",

@@ -17,8 +17,8 @@ from ._img import (
     SpecAugment,
     Warp1DGrid,
 )
-from ._feats import FeatureDeltas, MeanVarianceNormalization
-from ._pad import PadVariable
+from ._feats import ChunkTokenSequencesBySlices, FeatureDeltas, MeanVarianceNormalization, SliceSpectData
+from ._pad import ChunkBySlices, PadMaskedSequence, PadVariable
 from ._decoding import CTCGreedySearch, RandomWalk, SequenceLogProbabilities
 from ._lm import (
     ExtractableSequentialLanguageModel,
@@ -41,6 +41,10 @@ from ._string import (
 )
 
 __all__ = [
+    "ChunkBySlices",
+    "ChunkTokenSequencesBySlices",
+    "PadMaskedSequence",
+    "SliceSpectData",
     "ConcatSoftAttention",
     "DotProductSoftAttention",
     "GeneralizedDotProductSoftAttention",

@@ -79,7 +79,23 @@ int pdt_lev(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn,
             int64_t *ref_lens_out, int64_t *hyp_lens_out, int32_t *status, void *workspace,
             int64_t workspace_bytes, void *stream);
 
-/* The same call for inputs a previous pdt_lev has already classified into `workspace`: same ref /
+/* pdt_lev that also LEAVES its classification -- lengths, token classes, match tables -- in
+ * `workspace` for a following pdt_lev_classified.  (pdt_lev itself builds them inside its recurrence
+ * kernel where the shape allows and leaves nothing behind; this call always takes the two launches,
+ * classification then recurrence.)  Same results, same warning bits. */
+int pdt_lev_keep(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn,
+                 const int64_t *hyp, int64_t H, int64_t hyp_st, int64_t hyp_sn, int64_t N,
+                 int has_eos, int64_t eos, int include_eos, float ins_cost, float del_cost,
+                 float sub_cost, int norm, int mode, int exclude_last, float padding,
+                 int return_mistakes, float *out, int64_t out_sh, int64_t out_sn,
+                 int64_t *ref_lens_out, int64_t *hyp_lens_out, int32_t *status, void *workspace,
+                 int64_t workspace_bytes, void *stream);
+
+/* The same call for inputs a previous pdt_lev_keep has already classified into `workspace` (a
+ * workspace that no such call filled -- e.g. one that only a pdt_lev saw -- is recognised on the
+ * host and the call then classifies for itself, as pdt_lev does; that is a guard against the
+ * never-filled case only, keyed by the workspace's address, not a check that its tables are still
+ * valid -- what follows stays the caller's promise): same ref /
  * hyp contents, shapes and strides, same eos / include_eos, same workspace bytes untouched since,
  * issued on the same stream (or ordered after it).  On the bit-parallel path (unit costs) the
  * lengths, token classes and match tables are then read from the workspace instead of being rebuilt

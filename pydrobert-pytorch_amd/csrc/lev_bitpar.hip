@@ -22,6 +22,9 @@
 //                        the last reference token the vectors hold D[ref_len][h] - D[ref_len][h-1]
 //                        for every h: all prefix distances come out of one final prefix sum.
 // (With X = hyp the transposed table is computed; unit costs make it the same table.)
+// Where the plan says `fused` (four 16-lane utterances per workgroup, Y <= 512) the second kernel
+// does the first one's work itself -- classify_utterance, one wave per utterance, straight into the
+// LDS arrays the recurrence reads -- and a call is ONE launch that never touches the workspace.
 //
 // Optimal completion (unit costs, references of up to 512 tokens) has its own kernel at the end of
 // this file, oc_bitpar_kernel, with the bit-vectors along the REFERENCE: a row's profile is then a
@@ -66,6 +69,9 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 // words (conflict-free 16-byte accesses)
 constexpr int kBitparChunk = 16, kBitparLaneStride = 20;
 constexpr size_t kBitparRingBytes = (size_t)2 * PDT_WAVE * kBitparLaneStride * 4;
+constexpr int kFusedLensBytes = 32;  // fused lev_bitpar_kernel: (ref_len, hyp_len) of the workgroup's four utterances
+
+static size_t oc_fused_lds_bytes(int64_t X, int64_t Y);  // (the layout is with the kernel, below)
 
 // X: length of the bit-vector sequence, Y: of the consumed one.  Blocks are 32 rows and the
 // presence word has 32 bits: X <= 1024.
@@ -90,6 +96,19 @@ BitparPlan plan_bitpar(int64_t X, int64_t Y, int64_t N) {
   if (p.lds_sub * upw + tail(upw) > 150 * 1024 || p.lds_classify * 4 > 160 * 1024) return p;
   p.upw = upw;
   p.lds_tail = tail(upw);
+  // The fused form of lev_bitpar_kernel (classification inside the recurrence kernel): a 16-lane
+  // utterance per wave quarter, four waves = four utterances, the classes of Y in eight registers
+  // per lane, and the workgroup's LDS within the 40 KiB that keep four workgroups on a CU.  Every
+  // other shape keeps the two launches.
+  if (lgL == 4 && upw == 4 && Ys <= 8 * PDT_WAVE) {
+    const size_t sub_f = align_up(std::max(Xs, Ys) * 8 + (Xs + 1) * 4, 16);
+    if (sub_f * 4 + kFusedLensBytes + p.lds_tail <= 40 * 1024) {
+      p.fused = 1;
+      p.lds_sub_fused = sub_f;
+    }
+  }
+  // The same for oc_bitpar_kernel (X = reference, 16 lanes whatever its length; Y = hypothesis).
+  if (X <= 16 * 32 && Ys <= 8 * PDT_WAVE && oc_fused_lds_bytes(X, Y) <= 40 * 1024) p.oc_fused = 1;
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
@@ -104,29 +123,35 @@ BitparPlan plan_bitpar(int64_t X, int64_t Y, int64_t N) {
   return p;
 }
 
-// ---- kernel 1: lengths, classes, compressed match masks -------------------------------------
-// (Time-major inputs cost this kernel ~15 us at the bench shape -- a wave's tokens sit in 512
-// different 32-byte sectors; reading (T, 4) strips with the whole workgroup and exchanging them
-// through LDS measured no better.)
-template <int NR>
-__global__ void __launch_bounds__(256) lev_classify_kernel(const BitparArgs a, const int lds_per_wave) {
-  extern __shared__ __align__(16) unsigned char smem[];
+// ---- classification: lengths, classes, compressed match masks ---------------------------------
+// One wave, one utterance, the tables left in LDS.  Three layouts:
+//   kClassifyStaged   (lev_classify_kernel)  po, the token table (later the mask words) and the
+//                     classes of Y (`yc`, two bytes each) are separate regions; the caller sends
+//                     yh[j] = po[yc[j]] and the mask words to the workspace.
+//   kClassifyInPlace  (the fused form of lev_bitpar_kernel; Y <= 8 * 64)  `po`, `ctok` and `yh_l`
+//                     are ONE region of max(X, Y) * 8 bytes that holds, one after the other, the token
+//                     table / presence map, then po, then the finished yh -- the classes of Y wait
+//                     in registers while the region changes hands -- and `msk` is the recurrence's
+//                     own array: classification needs no LDS beyond what the recurrence reads.
+//   kClassifyPacked   (the fused form of oc_bitpar_kernel; X <= 512, Y <= 8 * 64)  po and yh are
+//                     ONE 32-bit word per entry (presence of the 16 blocks | offset << 16), the
+//                     classes of X go to LDS (`yc`, two bytes each, in position order) instead of
+//                     the workspace; the token table may share its bytes with `msk` and `yh_l`
+//                     (all written after it is dead), `po` and `yc` are scratch of their own.
+struct Classified {
+  int ref_len, hyp_len, x_len, y_len;
+};
+enum ClassifyMode { kClassifyStaged, kClassifyInPlace, kClassifyPacked };
+
+template <int NR, ClassifyMode MODE>
+__device__ __forceinline__ Classified classify_utterance(const BitparArgs &a, const int64_t n, uint2 *po,
+                                                         int64_t *ctok, unsigned *msk, short *yc, uint2 *yh_l) {
+  constexpr bool IN_PLACE = MODE != kClassifyStaged;  // (the classes of Y stay in registers)
+  constexpr bool PACKED = MODE == kClassifyPacked;
+  unsigned *po32 = reinterpret_cast<unsigned *>(po), *yh32 = reinterpret_cast<unsigned *>(yh_l);
   const int lane = lane_id();
-  const int wave = (int)(threadIdx.x >> 6);
-  // (time-major tokens: one 128-byte line of a row holds 16 neighbouring utterances' tokens = four
-  // workgroups; with the XCD-aware order those four run on ONE XCD and its L2 fetches the line once
-  // -- under the dispatcher's round-robin they sat on four XCDs and HBM delivered it four times)
-  const int64_t n = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
-  if (n >= a.N) return;  // waves never synchronise with each other
-  unsigned char *base = smem + (size_t)wave * lds_per_wave;
-  const int X = a.X > 0 ? a.X : 1, Y = a.Y > 0 ? a.Y : 1;
-  // [(presence, offset) per class: X * 8] [distinct tokens (X + 1) * 8; later the packed mask
-  // words] [classes of Y, 2 bytes each]
-  uint2 *po = reinterpret_cast<uint2 *>(base);
-  int64_t *ctok = reinterpret_cast<int64_t *>(base + (size_t)X * 8);
-  unsigned *msk = reinterpret_cast<unsigned *>(ctok);
+  const int X = a.X > 0 ? a.X : 1;
   uint2 *pmap = reinterpret_cast<uint2 *>(ctok);  // (instead of the token table: one or the other)
-  short *yc = reinterpret_cast<short *>(ctok + max(X + 1, kDirectWords));
 
   // ---- lengths (_string.py:195-228) -----------------------------------------------------
   int ref_len = a.R, hyp_len = a.H;
@@ -172,12 +197,12 @@ __global__ void __launch_bounds__(256) lev_classify_kernel(const BitparArgs a, c
     lgP = search_depth(U);
     classes_of<NR>(ctok, U, lgP, xt, xc);
   }
-  for (int k = lane; k < U; k += PDT_WAVE) po[k] = make_uint2(0u, 0u);
-  if (oc) {
+  if (oc && !PACKED) {
 #pragma unroll
     for (int q = 0; q < NR; ++q)
       if (lane + q * PDT_WAVE < x_len) a.xcls[n * (int64_t)X + lane + q * PDT_WAVE] = (uint16_t)xc[q];
   }
+  int cy[8] = {-1, -1, -1, -1, -1, -1, -1, -1};  // IN_PLACE: the classes of Y[lane + 64 q]
   for (int j0 = 0; j0 < y_len; j0 += 8 * PDT_WAVE) {
     int64_t yt[8];
     int c[8];
@@ -185,48 +210,77 @@ __global__ void __launch_bounds__(256) lev_classify_kernel(const BitparArgs a, c
     if (direct) classes_from_map<8>(pmap, yt, c);
     else classes_of<8>(ctok, U, lgP, yt, c);
 #pragma unroll
-    for (int q = 0; q < 8; ++q)
-      if (j0 + lane + q * PDT_WAVE < y_len) yc[j0 + lane + q * PDT_WAVE] = (short)c[q];
+    for (int q = 0; q < 8; ++q) {
+      if (IN_PLACE) cy[q] = c[q];
+      else if (j0 + lane + q * PDT_WAVE < y_len) yc[j0 + lane + q * PDT_WAVE] = (short)c[q];
+    }
   }
-  wave_sync();  // the token table is dead from here on: the mask words take it over
+  // The token table is dead from here on: po (kClassifyInPlace) / the mask words take it over.
+  // (Only that overlay needs po zeroed this late; for the standalone kernel, whose po is a region of
+  // its own, the place is as good as any.)
+  wave_sync();
+  if (PACKED) {
+    for (int k = lane; k < U; k += PDT_WAVE) po32[k] = 0u;
+#pragma unroll
+    for (int q = 0; q < NR; ++q)
+      if (lane + q * PDT_WAVE < x_len) yc[lane + q * PDT_WAVE] = (short)xc[q];
+  } else {
+    for (int k = lane; k < U; k += PDT_WAVE) po[k] = make_uint2(0u, 0u);
+  }
   for (int i = lane; i <= x_len; i += PDT_WAVE) msk[i] = 0u;
+  wave_sync();
   auto for_x = [&](auto &&f) {  // f(position, class) over this lane's positions of X
 #pragma unroll
     for (int q = 0; q < NR; ++q)
       if (lane + q * PDT_WAVE < x_len) f(lane + q * PDT_WAVE, xc[q]);
   };
-  for_x([&](const int i, const int c) {
-    atomicOr(&po[c].x, 1u << (i >> 5));  // blocks that hold the class
+  for_x([&](const int i, const int c) {  // blocks that hold the class
+    if (PACKED) atomicOr(&po32[c], 1u << (i >> 5));
+    else atomicOr(&po[c].x, 1u << (i >> 5));
   });
   wave_sync();
   {  // offsets = exclusive scan of the presence popcounts
     const int B = (U + PDT_WAVE - 1) / PDT_WAVE;
     const int i0 = lane * B;
+    auto presence = [&](const int k) { return PACKED ? po32[k] : po[k].x; };
     int sum = 0;
     for (int q = 0; q < B; ++q)
-      if (i0 + q < U) sum += __popc(po[i0 + q].x);
+      if (i0 + q < U) sum += __popc(presence(i0 + q));
     const int incl = wave_incl_scan_add(sum);
     int pos = incl - sum;
     for (int q = 0; q < B; ++q)
       if (i0 + q < U) {
-        po[i0 + q].y = (unsigned)pos;
-        pos += __popc(po[i0 + q].x);
+        const int cnt = __popc(presence(i0 + q));
+        if (PACKED) po32[i0 + q] |= (unsigned)pos << 16;
+        else po[i0 + q].y = (unsigned)pos;
+        pos += cnt;
       }
   }
   wave_sync();
   for_x([&](const int i, const int c) {
-    const uint2 e = po[c];
+    uint2 e;
+    if (PACKED) e = make_uint2(po32[c] & 0xffffu, po32[c] >> 16);
+    else e = po[c];
     atomicOr(&msk[e.y + (unsigned)__popc(e.x & ((1u << (i >> 5)) - 1u))], 1u << (i & 31));
   });
   wave_sync();
-  for (int j = lane; j < y_len; j += PDT_WAVE) {
-    const int c = yc[j];
-    a.yh[n * (int64_t)Y + j] = c >= 0 ? po[c] : make_uint2(0u, 0u);
+  if (PACKED) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (lane + q * PDT_WAVE < y_len) yh32[lane + q * PDT_WAVE] = cy[q] >= 0 ? po32[cy[q]] : 0u;
+    if (y_len == 0 && lane == 0) yh32[0] = 0u;  // (the entry the clamped look-ups read)
+  } else if (IN_PLACE) {  // yh over po: every look-up is in a register before the first entry is written
+    uint2 v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      v[q] = (lane + q * PDT_WAVE < y_len && cy[q] >= 0) ? po[cy[q]] : make_uint2(0u, 0u);
+    wave_sync();
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+      if (lane + q * PDT_WAVE < y_len) yh_l[lane + q * PDT_WAVE] = v[q];
+    if (y_len == 0 && lane == 0) yh_l[0] = make_uint2(0u, 0u);  // (the entry the clamped look-ups read)
   }
-  for (int i = lane; i <= x_len; i += PDT_WAVE) a.msk[n * (int64_t)(X + 1) + i] = msk[i];
   if (lane == 0) {
-    a.lens[2 * n] = ref_len;
-    a.lens[2 * n + 1] = hyp_len;
     int flags = 0;
     if (rmiss) flags |= PDT_WARN_REF_NO_EOS;
     if (hmiss) flags |= PDT_WARN_HYP_NO_EOS;
@@ -235,35 +289,104 @@ __global__ void __launch_bounds__(256) lev_classify_kernel(const BitparArgs a, c
     if (a.ref_lens_out) a.ref_lens_out[n] = ref_len;
     if (a.hyp_lens_out) a.hyp_lens_out[n] = hyp_len;
   }
+  return Classified{ref_len, hyp_len, x_len, y_len};
+}
+
+// ---- kernel 1: classification into the workspace ------------------------------------------------
+// (Time-major inputs cost this kernel ~15 us at the bench shape -- a wave's tokens sit in 512
+// different 32-byte sectors; reading (T, 4) strips with the whole workgroup and exchanging them
+// through LDS measured no better.)
+template <int NR>
+__global__ void __launch_bounds__(256) lev_classify_kernel(const BitparArgs a, const int lds_per_wave) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int lane = lane_id();
+  const int wave = (int)(threadIdx.x >> 6);
+  // (time-major tokens: one 128-byte line of a row holds 16 neighbouring utterances' tokens = four
+  // workgroups; with the XCD-aware order those four run on ONE XCD and its L2 fetches the line once
+  // -- under the dispatcher's round-robin they sat on four XCDs and HBM delivered it four times)
+  const int64_t n = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * 4 + wave;
+  if (n >= a.N) return;  // waves never synchronise with each other
+  unsigned char *base = smem + (size_t)wave * lds_per_wave;
+  const int X = a.X > 0 ? a.X : 1, Y = a.Y > 0 ? a.Y : 1;
+  // [(presence, offset) per class: X * 8] [distinct tokens (X + 1) * 8; later the packed mask
+  // words] [classes of Y, 2 bytes each]
+  uint2 *po = reinterpret_cast<uint2 *>(base);
+  int64_t *ctok = reinterpret_cast<int64_t *>(base + (size_t)X * 8);
+  unsigned *msk = reinterpret_cast<unsigned *>(ctok);
+  short *yc = reinterpret_cast<short *>(ctok + max(X + 1, kDirectWords));
+  const Classified c = classify_utterance<NR, kClassifyStaged>(a, n, po, ctok, msk, yc, nullptr);
+  for (int j = lane; j < c.y_len; j += PDT_WAVE) {
+    const int k = yc[j];
+    a.yh[n * (int64_t)Y + j] = k >= 0 ? po[k] : make_uint2(0u, 0u);
+  }
+  for (int i = lane; i <= c.x_len; i += PDT_WAVE) a.msk[n * (int64_t)(X + 1) + i] = msk[i];
+  if (lane == 0) {
+    a.lens[2 * n] = c.ref_len;
+    a.lens[2 * n + 1] = c.hyp_len;
+  }
 }
 
 // ---- kernel 2: the column recurrence ----------------------------------------------------------
 // Two waves per workgroup: wave 1 looks the match words up one chunk of steps ahead and leaves
 // them in an LDS ring, wave 0 runs the recurrence -- a lone wave issues an instruction every ~5.5
 // cycles whatever it is, and the look-ups were 12 of the loop's 40 instructions per step.
-__global__ void __launch_bounds__(128) lev_bitpar_kernel(const BitparArgs a, const int lds_per_sub, const int ring_off) {
+//
+// FUSED (plan.fused: four utterances per workgroup, X <= 512, Y <= 512): the workgroup starts with
+// four waves and each classifies one of its four utterances straight into that utterance's tables
+// (classify_utterance<8, kClassifyInPlace>); after one barrier waves 2 and 3 leave and waves 0 and 1 carry on as
+// below.  No classification launch, no tables in the workspace, nothing to stage.  An utterance's
+// region is [max(X, Y) * 8: token table, then po, then yh] [(X + 1) * 4: mask words]; the lengths of
+// the four sit in the 32 bytes in front of the ring.
+template <bool FUSED>
+__device__ __forceinline__ void lev_bitpar_body(const BitparArgs &a, const int lds_per_sub, const int ring_off) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
   const int L = 1 << a.lgL;
   const int sub = lane >> a.lgL, b = lane & (L - 1);
-  const int64_t n_raw = (int64_t)blockIdx.x * a.upw + sub;
+  // (FUSED: the classification's workgroup order -- its token reads are what the order is for)
+  const int64_t grp = FUSED ? (int64_t)xcd_remap(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int64_t n_raw = grp * a.upw + sub;
   const bool valid = sub < a.upw && n_raw < a.N;
-  const int64_t n = valid ? n_raw : (int64_t)blockIdx.x * a.upw;  // (a safe utterance to address)
+  const int64_t n = valid ? n_raw : grp * a.upw;  // (a safe utterance to address)
   const int X = a.X > 0 ? a.X : 1, Y = a.Y > 0 ? a.Y : 1;
+  const int yh_cap = FUSED ? max(X, Y) : Y;  // entries of the region that yh shares (FUSED) or owns
   unsigned char *base = smem + (size_t)(valid ? sub : 0) * lds_per_sub;
   uint2 *yh_l = reinterpret_cast<uint2 *>(base);
-  unsigned *msk_l = reinterpret_cast<unsigned *>(yh_l + Y);
+  unsigned *msk_l = reinterpret_cast<unsigned *>(yh_l + yh_cap);
   unsigned *ring = reinterpret_cast<unsigned *>(smem + ring_off);
   float *bnd = reinterpret_cast<float *>(smem + ring_off) + (size_t)(valid ? sub : 0) * (X + 1);  // (after the loop)
 
-  const int ref_len = a.lens[2 * n], hyp_len = a.lens[2 * n + 1];
+  int ref_len, hyp_len;
+  if (FUSED) {
+    int32_t *lens_l = reinterpret_cast<int32_t *>(smem + ring_off - kFusedLensBytes);
+    const int64_t nw = grp * 4 + wave;  // wave w classifies utterance w of the group
+    if (nw < a.N) {
+      unsigned char *r = smem + (size_t)wave * lds_per_sub;
+      const Classified c = classify_utterance<8, kClassifyInPlace>(
+          a, nw, reinterpret_cast<uint2 *>(r), reinterpret_cast<int64_t *>(r),
+          reinterpret_cast<unsigned *>(r + (size_t)yh_cap * 8), nullptr, reinterpret_cast<uint2 *>(r));
+      if (lane == 0) {
+        lens_l[2 * wave] = c.ref_len;
+        lens_l[2 * wave + 1] = c.hyp_len;
+      }
+    }
+    __syncthreads();
+    // (16 waves per CU up to here instead of 8; a wave that has ended no longer counts at a barrier,
+    // so the loop's barriers below are between waves 0 and 1 as in the staged kernel)
+    if (wave >= 2) return;
+    ref_len = lens_l[2 * (valid ? sub : 0)];
+    hyp_len = lens_l[2 * (valid ? sub : 0) + 1];
+  } else {
+    ref_len = a.lens[2 * n];
+    hyp_len = a.lens[2 * n + 1];
+  }
   int Heff = a.exclude_last ? hyp_len - 1 : hyp_len;
   if (Heff < 0) Heff = 0;
   const int x_len = valid ? Heff : 0, y_len = valid ? ref_len : 0;
 
   // ---- stage this utterance's lookups in LDS (eight loads in flight per lane) --------------
-  {
+  if (!FUSED) {
     const uint2 *src = a.yh + n * (int64_t)Y;
     for (int j0 = b + wave * 8 * L; j0 < y_len; j0 += 16 * L) {
       uint2 v[8];
@@ -283,8 +406,8 @@ __global__ void __launch_bounds__(128) lev_bitpar_kernel(const BitparArgs a, con
       for (int q = 0; q < 8; ++q)
         if (i0 + q * L <= x_len) msk_l[i0 + q * L] = v[q];
     }
+    __syncthreads();
   }
-  __syncthreads();
   int ymax = y_len;
 #pragma unroll
   for (int t = 1; t < PDT_WAVE; t <<= 1) ymax = max(ymax, __shfl_xor(ymax, t));
@@ -444,6 +567,15 @@ __global__ void __launch_bounds__(128) lev_bitpar_kernel(const BitparArgs a, con
   }
 }
 
+__global__ void __launch_bounds__(256) lev_bitpar_kernel(const BitparArgs a, const int lds_per_sub, const int ring_off) {
+  lev_bitpar_body<true>(a, lds_per_sub, ring_off);
+}
+
+// the recurrence alone, on tables that lev_classify_kernel left in the workspace
+__global__ void __launch_bounds__(128) lev_bitpar_staged_kernel(const BitparArgs a, const int lds_per_sub, const int ring_off) {
+  lev_bitpar_body<false>(a, lds_per_sub, ring_off);
+}
+
 // host side -------------------------------------------------------------------------------
 static int set_lds(const void *kern, size_t smem) {
   if (smem > 64 * 1024) {
@@ -453,8 +585,8 @@ static int set_lds(const void *kern, size_t smem) {
   return 0;
 }
 
-// LevArgs -> the three launches.  `ws` must hold plan.total bytes.
-int launch_lev_bitpar(const LevArgs &la, const BitparPlan &p, void *ws, hipStream_t stream, bool classified) {
+// LevArgs -> the launches.  `ws` must hold plan.total bytes.
+int launch_lev_bitpar(const LevArgs &la, const BitparPlan &p, void *ws, hipStream_t stream, LevTables tables) {
   BitparArgs a{};
   a.ref = la.ref; a.hyp = la.hyp;
   a.ref_st = la.ref_st; a.ref_sn = la.ref_sn; a.hyp_st = la.hyp_st; a.hyp_sn = la.hyp_sn;
@@ -473,7 +605,16 @@ int launch_lev_bitpar(const LevArgs &la, const BitparPlan &p, void *ws, hipStrea
   a.msk = reinterpret_cast<uint32_t *>(w + p.off_msk);
 
   int rc = 0;
-  if (!classified) {  // (pdt_lev_classified: the workspace holds these inputs' tables already)
+  if (tables == kTablesOwn && p.fused) {  // one launch, nothing goes through the workspace
+    const size_t smem = p.lds_sub_fused * 4 + kFusedLensBytes + p.lds_tail;
+    auto kern = lev_bitpar_kernel;
+    rc = set_lds(reinterpret_cast<const void *>(kern), smem);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((a.N + 3) / 4)), dim3(256), smem, stream, a, (int)p.lds_sub_fused,
+                       (int)(p.lds_sub_fused * 4 + kFusedLensBytes));
+    return (int)hipGetLastError();
+  }
+  if (tables != kTablesGiven) {  // (pdt_lev_classified: the workspace holds these inputs' tables already)
     auto ck = a.X <= 8 * PDT_WAVE ? lev_classify_kernel<8> : lev_classify_kernel<16>;
     rc = set_lds(reinterpret_cast<const void *>(ck), p.lds_classify * 4);
     if (rc) return rc;
@@ -482,7 +623,7 @@ int launch_lev_bitpar(const LevArgs &la, const BitparPlan &p, void *ws, hipStrea
   }
   const size_t smem = p.lds_sub * p.upw + p.lds_tail;
   const unsigned grid = (unsigned)((a.N + p.upw - 1) / p.upw);
-  auto kern = lev_bitpar_kernel;
+  auto kern = lev_bitpar_staged_kernel;
   rc = set_lds(reinterpret_cast<const void *>(kern), smem);
   if (rc) return rc;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(128), smem, stream, a, (int)p.lds_sub, (int)(p.lds_sub * p.upw));
@@ -760,25 +901,45 @@ __device__ __forceinline__ unsigned oc_spread(const OcSpread &sp, unsigned x) {
 // (block minima, row minimum, spreading, class bits, the store).  A lone wave issues an instruction
 // every ~5.5 cycles; with the waves of four such workgroups on a CU every SIMD has several to pick
 // from.  Roles rotate with the workgroup index so that producers do not all land on one SIMD.
+//
+// FUSED (the plan's oc_fused: hypotheses of up to 512 tokens, LDS within 40 KiB): the four waves first
+// classify the group's four utterances, one each (classify_utterance<8, kClassifyPacked>), and only
+// then take their roles.  An utterance's region is [match words][yh, ONE word per hypothesis token:
+// presence of the 16 blocks | offset << 16][classes in spread order]; the token table lies over the
+// whole region while it lives, the per-class words and the classes in position order use the
+// passes' ring, which nobody writes before the roles start.  Nothing but `class_tokens` -- the
+// call's output -- goes to memory, and the producer reads its look-ups from LDS instead of
+// fetching them 16 rows ahead.
 struct OcLds {
   size_t flags, ring, bm, sub, total;  // byte offsets; sub = first utterance's tables
   size_t per_sub;
+  size_t yh, scratch;  // FUSED: yh inside an utterance's region; a wave's share of the ring while classifying
 };
-static __host__ __device__ inline OcLds oc_lds(const int X, const int NC) {
+constexpr size_t kOcLensOff = 128;  // FUSED: (ref_len, hyp_len) x 4 behind the ring's flags
+static __host__ __device__ inline OcLds oc_lds(const int X, const int Y, const int NC, const bool fused) {
   OcLds l;
-  const size_t Xs = (size_t)(X > 0 ? X : 1);
+  const size_t Xs = (size_t)(X > 0 ? X : 1), Ys = (size_t)(Y > 0 ? Y : 1);
   const int S = PDT_OC_SLOTS(NC);
   l.flags = 1024;                                          // after the 256-entry table (room for 32-bit entries)
   l.ring = l.flags + 256;                                  // ready[S], done[S]
   l.bm = l.ring + (size_t)S * kOcChunk * PDT_WAVE * 8;     // a slot: kOcChunk rows of (Pv, Mv) per lane
   l.sub = l.bm + (size_t)NC * kOcChunk * PDT_WAVE * 4;     // per consumer: kOcChunk rows of 16 words per utterance
   l.per_sub = ((Xs + 1) * 4 + 15) / 16 * 16 + 256 + 512 * 2;  // match words; 2 x 16 look-ups; classes in spread order
+  l.yh = l.scratch = 0;
+  if (fused) {
+    l.yh = ((Xs + 1) * 4 + 15) / 16 * 16;
+    l.per_sub = l.yh + (Ys * 4 + 15) / 16 * 16 + 512 * 2;
+    const size_t tab = Xs * 8 > (size_t)kDirectWords * 8 ? Xs * 8 : (size_t)kDirectWords * 8;  // token table / presence map
+    if (l.per_sub < tab) l.per_sub = tab;
+    l.scratch = (l.bm - l.ring) / 4;  // >= X * 4 (per-class words) + X * 2 (classes): 3 072 B at S = 6
+  }
   l.total = l.sub + 4 * l.per_sub;
   return l;
 }
 
-template <int NC>
-__global__ void __launch_bounds__(64 * (NC + 1)) oc_bitpar_kernel(const OcBitArgs a) {
+template <int NC, bool FUSED>
+__device__ __forceinline__ void oc_bitpar_body(const OcBitArgs &a, const BitparArgs &ca) {
+  static_assert(!FUSED || NC == 3, "the fused form classifies with the workgroup's four waves");
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr int S = PDT_OC_SLOTS(NC), kChunk = kOcChunk, NG = 8;
 #if PDT_OC_TABLE32
@@ -788,29 +949,58 @@ __global__ void __launch_bounds__(64 * (NC + 1)) oc_bitpar_kernel(const OcBitArg
   uint16_t *tab = reinterpret_cast<uint16_t *>(smem);
   oc_build_table<4>(tab);
 #endif
-  const OcLds L = oc_lds(a.X, NC);
+  const OcLds L = oc_lds(a.X, a.Y, NC, FUSED);
   int *ready = reinterpret_cast<int *>(smem + L.flags), *done = ready + S;
   uint2 *ring = reinterpret_cast<uint2 *>(smem + L.ring);
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6);
-  const int role = (wave + (int)blockIdx.x) % (NC + 1);  // 0: producer, 1 .. NC: consumers
+  // (FUSED: the classification's workgroup order -- its token reads are what the order is for)
+  const int64_t grp = FUSED ? (int64_t)xcd_remap(blockIdx.x, gridDim.x) : (int64_t)blockIdx.x;
+  const int role = (wave + (int)grp) % (NC + 1);  // 0: producer, 1 .. NC: consumers
   const int q = lane >> 4, b = lane & 15;
-  const int64_t n_raw = (int64_t)blockIdx.x * 4 + q;
+  const int64_t n_raw = grp * 4 + q;
   const bool valid = n_raw < a.N;
   const int64_t n = valid ? n_raw : (int64_t)a.N - 1;
   const int X = a.X > 0 ? a.X : 1, Y = a.Y > 0 ? a.Y : 1;
   unsigned char *base = smem + L.sub + (size_t)q * L.per_sub;
   unsigned *msk_l = reinterpret_cast<unsigned *>(base);
   uint16_t *xc_l = reinterpret_cast<uint16_t *>(base + L.per_sub - 1024);
+  const unsigned *yh_l = reinterpret_cast<const unsigned *>(base + L.yh);  // (FUSED)
 
-  const int ref_len = valid ? a.lens[2 * n] : 0, hyp_len = valid ? a.lens[2 * n + 1] : 0;
+  int ref_len, hyp_len;
+  const uint16_t *csrc;
+  if (FUSED) {
+    int32_t *lens_l = reinterpret_cast<int32_t *>(smem + L.flags + kOcLensOff);
+    const int64_t nw = grp * 4 + wave;  // wave w classifies utterance w of the group
+    if (nw < a.N) {
+      unsigned char *r = smem + L.sub + (size_t)wave * L.per_sub, *scr = smem + L.ring + (size_t)wave * L.scratch;
+      const Classified c = classify_utterance<8, kClassifyPacked>(
+          ca, nw, reinterpret_cast<uint2 *>(scr), reinterpret_cast<int64_t *>(r), reinterpret_cast<unsigned *>(r),
+          reinterpret_cast<short *>(scr + (size_t)X * 4), reinterpret_cast<uint2 *>(r + L.yh));
+      if (lane == 0) {
+        lens_l[2 * wave] = c.ref_len;
+        lens_l[2 * wave + 1] = c.hyp_len;
+      }
+    } else if (lane == 0) {
+      // (no such utterance: its quarter of the producer still runs the rows, on look-up 0 = no match)
+      *reinterpret_cast<unsigned *>(smem + L.sub + (size_t)wave * L.per_sub + L.yh) = 0u;
+    }
+    __syncthreads();
+    ref_len = valid ? lens_l[2 * q] : 0;
+    hyp_len = valid ? lens_l[2 * q + 1] : 0;
+    csrc = reinterpret_cast<const uint16_t *>(smem + L.ring + (size_t)(valid ? q : 0) * L.scratch + (size_t)X * 4);
+  } else {
+    ref_len = valid ? a.lens[2 * n] : 0;
+    hyp_len = valid ? a.lens[2 * n + 1] : 0;
+    csrc = a.xcls + n * (int64_t)X;
+  }
   int Heff = a.exclude_last ? hyp_len - 1 : hyp_len;
   if (Heff < 0) Heff = 0;
   if (threadIdx.x < 2 * S) ready[threadIdx.x] = 0;
   const OcSpread sp = oc_spread_setup(b);
-  const uint16_t *csrc = a.xcls + n * (int64_t)X;
   const int rank0 = ref_len > 0 ? (int)csrc[0] : 0;  // class of ref[0]
-  if (role == 0) {  // the match words of this utterance: 16 lanes, eight loads in flight each
+  if (FUSED && role == 0) {  // (the match words are where the classification built them)
+  } else if (role == 0) {  // the match words of this utterance: 16 lanes, eight loads in flight each
     const unsigned *msrc = a.msk + n * (int64_t)(X + 1);
     for (int i0 = b; i0 <= ref_len; i0 += 8 * 16) {
       unsigned v[8];
@@ -877,16 +1067,25 @@ __global__ void __launch_bounds__(64 * (NC + 1)) oc_bitpar_kernel(const OcBitArg
     // rows ahead (a load per pass would cost its whole latency every pass) and leaves it in LDS
     static_assert(16 % kChunk == 0, "a block of look-ups is a whole number of passes");
     uint2 *ybuf = reinterpret_cast<uint2 *>(base + L.per_sub - 1024 - 256);
-    uint2 pre = Heff > 0 ? ysrc[min(b, jcap)] : make_uint2(0u, 0u);
+    uint2 pre = make_uint2(0u, 0u);
+    if (!FUSED) pre = Heff > 0 ? ysrc[min(b, jcap)] : make_uint2(0u, 0u);
     for (int i = 0; i < nchunks; ++i) {
-      if ((i * kChunk) % 16 == 0) {
-        const int blk = (i * kChunk) >> 4;
-        ybuf[(blk & 1) * 16 + b] = pre;
-        pre = Heff > 0 ? ysrc[min((blk + 1) * 16 + b, jcap)] : make_uint2(0u, 0u);
-      }
       uint2 hq[kChunk];
+      if (FUSED) {  // (rows past the hypothesis read its last entry, as the clamped fetches below do)
 #pragma unroll
-      for (int r = 0; r < kChunk; ++r) hq[r] = ybuf[(i * kChunk + r) & 31];
+        for (int r = 0; r < kChunk; ++r) {
+          const unsigned v = yh_l[min(i * kChunk + r, jcap)];
+          hq[r] = make_uint2(v & 0xffffu, v >> 16);
+        }
+      } else {
+        if ((i * kChunk) % 16 == 0) {
+          const int blk = (i * kChunk) >> 4;
+          ybuf[(blk & 1) * 16 + b] = pre;
+          pre = Heff > 0 ? ysrc[min((blk + 1) * 16 + b, jcap)] : make_uint2(0u, 0u);
+        }
+#pragma unroll
+        for (int r = 0; r < kChunk; ++r) hq[r] = ybuf[(i * kChunk + r) & 31];
+      }
       unsigned eq[kChunk];
 #pragma unroll
       for (int r = 0; r < kChunk; ++r) eq[r] = msk_l[hq[r].y + (unsigned)__popc(hq[r].x & lowmask)];
@@ -1033,7 +1232,25 @@ __global__ void __launch_bounds__(64 * (NC + 1)) oc_bitpar_kernel(const OcBitArg
   if (valid && b == 0 && a.max_count && max_cnt > 0) atomicMax(a.max_count, max_cnt);
 }
 
+template <int NC>
+__global__ void __launch_bounds__(64 * (NC + 1)) oc_bitpar_kernel(const OcBitArgs a, const BitparArgs ca) {
+  oc_bitpar_body<NC, true>(a, ca);
+}
+
+// the mask kernel alone, on tables that lev_classify_kernel left in the workspace
+template <int NC>
+__global__ void __launch_bounds__(64 * (NC + 1)) oc_bitpar_staged_kernel(const OcBitArgs a) {
+  oc_bitpar_body<NC, false>(a, BitparArgs{});
+}
+
 constexpr int64_t kOcBitparMaxR = 512;  // 16 lanes of 32 columns
+
+// (a ring too small for the classification's scratch -- other PDT_OC_SLOTS / PDT_OC_CHUNK -- reads as
+// "does not fit": two launches)
+static size_t oc_fused_lds_bytes(int64_t X, int64_t Y) {
+  const OcLds l = oc_lds((int)X, (int)Y, PDT_OC_CONSUMERS, true);
+  return l.scratch >= (size_t)(X > 0 ? X : 1) * 6 ? l.total : ~(size_t)0;
+}
 
 int64_t oc_bitpar_workspace_bytes(int64_t R, int64_t H, int64_t N) {
   if (R > kOcBitparMaxR || H < 0 || N <= 0) return 0;
@@ -1066,11 +1283,6 @@ int launch_oc_mask_bitpar(const LevArgs &la, void *ws, int64_t ws_bytes, hipStre
   a.oc = 1;
   a.class_tokens = la.class_tokens;
   a.xcls = reinterpret_cast<uint16_t *>(w + p.total);
-  auto ck = lev_classify_kernel<8>;
-  int rc = set_lds(reinterpret_cast<const void *>(ck), p.lds_classify * 4);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ck, dim3((unsigned)((a.N + 3) / 4)), dim3(256), p.lds_classify * 4, stream, a,
-                     (int)p.lds_classify);
 
   OcBitArgs o{};
   o.N = la.N; o.X = la.R; o.Y = la.H; o.W = la.W;
@@ -1079,8 +1291,22 @@ int launch_oc_mask_bitpar(const LevArgs &la, void *ws, int64_t ws_bytes, hipStre
   o.lens = a.lens; o.yh = a.yh; o.msk = a.msk; o.xcls = a.xcls;
   o.bitmask = la.bitmask; o.max_count = la.max_count;
   constexpr int NC = PDT_OC_CONSUMERS;
-  const OcLds L = oc_lds(o.X, NC);
-  auto kern = oc_bitpar_kernel<NC>;
+  int rc = 0;
+  if (p.oc_fused) {  // one launch: nothing but class_tokens leaves the kernel's classification
+    const OcLds L = oc_lds(o.X, o.Y, NC, true);
+    auto kern = oc_bitpar_kernel<NC>;
+    rc = set_lds(reinterpret_cast<const void *>(kern), L.total);
+    if (rc) return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((la.N + 3) / 4)), dim3(64 * (NC + 1)), L.total, stream, o, a);
+    return (int)hipGetLastError();
+  }
+  auto ck = lev_classify_kernel<8>;
+  rc = set_lds(reinterpret_cast<const void *>(ck), p.lds_classify * 4);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ck, dim3((unsigned)((a.N + 3) / 4)), dim3(256), p.lds_classify * 4, stream, a,
+                     (int)p.lds_classify);
+  const OcLds L = oc_lds(o.X, o.Y, NC, false);
+  auto kern = oc_bitpar_staged_kernel<NC>;
   rc = set_lds(reinterpret_cast<const void *>(kern), L.total);
   if (rc) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)((la.N + 3) / 4)), dim3(64 * (NC + 1)), L.total, stream, o);

@@ -34,7 +34,14 @@ struct BitparPlan {
   size_t lds_classify, lds_sub;  // bytes: per wave / per utterance
   size_t lds_tail;               // bytes per workgroup after the utterances' tables (ring of match words, then distances)
   size_t off_lens, off_yh, off_msk, total;  // workspace
+  int fused;             // lev_bitpar_kernel classifies its own utterances (one launch, no tables in the workspace)
+  size_t lds_sub_fused;  // bytes per utterance in that form
+  int oc_fused;          // the same for oc_bitpar_kernel (plan of (R, H))
 };
+// Where the recurrence's tables come from: built by the call for itself (inside the recurrence
+// kernel where plan.fused), built into the workspace and left there for a later call
+// (pdt_lev_keep), or read from the workspace as such a call left them (pdt_lev_classified).
+enum LevTables { kTablesOwn, kTablesKeep, kTablesGiven };
 BitparPlan plan_bitpar(int64_t X, int64_t Y, int64_t N);
 
 // Stage one utterance's tokens tok[t*st + off], t < T, into LDS as int32 and return the

@@ -8,11 +8,12 @@
 #include "lev_common.hpp"
 #include "switches.hpp"
 #include <cstring>
+#include <mutex>
 
 namespace pdt {
 int launch_lev_skewed(LevArgs a, hipStream_t stream);
 int launch_lev_rowsync(LevArgs a, bool exact, hipStream_t stream);
-int launch_lev_bitpar(const LevArgs &la, const BitparPlan &p, void *ws, hipStream_t stream, bool classified);
+int launch_lev_bitpar(const LevArgs &la, const BitparPlan &p, void *ws, hipStream_t stream, LevTables tables);
 int launch_oc_mask_generic(const LevArgs &a, bool inexact, void *ws, int64_t ws_bytes, hipStream_t stream);
 int launch_oc_mask_bitpar(const LevArgs &a, void *ws, int64_t ws_bytes, hipStream_t stream);
 int64_t oc_bitpar_workspace_bytes(int64_t R, int64_t H, int64_t N);
@@ -82,6 +83,32 @@ Switches &switches() {
   return s;
 }
 
+// Workspaces whose tables the last bit-parallel call on them left in place (pdt_lev_keep, or pdt_lev
+// on a shape that takes the two launches).  pdt_lev_classified trusts a workspace only while it is
+// listed; a pdt_lev that classified inside its kernel delists the one it was given.  Host state
+// only: a few pointers behind a mutex, nothing on the launch path touches the device for it.
+namespace {
+std::mutex g_kept_mu;
+const void *g_kept[16] = {};
+unsigned g_kept_next = 0;
+}  // namespace
+static void kept_tables_forget(const void *ws) {
+  std::lock_guard<std::mutex> lock(g_kept_mu);
+  for (const void *&e : g_kept)
+    if (e == ws) e = nullptr;
+}
+static void kept_tables_note(const void *ws) {
+  kept_tables_forget(ws);
+  std::lock_guard<std::mutex> lock(g_kept_mu);
+  g_kept[g_kept_next++ % 16] = ws;
+}
+static bool kept_tables_has(const void *ws) {
+  std::lock_guard<std::mutex> lock(g_kept_mu);
+  for (const void *e : g_kept)
+    if (e == ws) return true;
+  return false;
+}
+
 static int fill_common(LevArgs &a, const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn,
                        const int64_t *hyp, int64_t H, int64_t hyp_st, int64_t hyp_sn, int64_t N,
                        int has_eos, int64_t eos, int include_eos, float ins, float del, float sub) {
@@ -117,6 +144,11 @@ extern "C" {
 //     and, with no entry point changed, the switch PDT_WALK_TABLE moved to the host package (no native code read it)
 //     then, additively: pdt_attn_dot, pdt_attn_dot_backward, pdt_attn_pool, pdt_attn_pool_backward,
 //     pdt_attn_workspace_bytes
+//     then: pdt_lev_keep.  pdt_lev CHANGED underneath -- where the shape allows it classifies inside
+//     the recurrence kernel and leaves no tables in the workspace -- so pdt_lev_classified now checks
+//     that the workspace it is given was filled by a call that keeps its tables (kept_tables below)
+//     and classifies for itself otherwise: the sequence pdt_lev, pdt_lev_classified of earlier
+//     callers keeps its results (the version stays 12)
 int pdt_amd_abi_version(void) { return 12; }
 
 int pdt_amd_set_switch(const char *name, int value) {
@@ -151,7 +183,7 @@ static int lev_entry(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_
                      int include_eos, float ins_cost, float del_cost, float sub_cost, int norm, int mode,
                      int exclude_last, float padding, int return_mistakes, float *out, int64_t out_sh,
                      int64_t out_sn, int64_t *ref_lens_out, int64_t *hyp_lens_out, int32_t *status,
-                     void *workspace, int64_t workspace_bytes, void *stream, bool classified) {
+                     void *workspace, int64_t workspace_bytes, void *stream, pdt::LevTables tables) {
   using namespace pdt;
   if (mode != PDT_MODE_FINAL && mode != PDT_MODE_PREFIX) return PDT_E_ARG;
   if (exclude_last && mode != PDT_MODE_PREFIX) return PDT_E_ARG;  // _string.py:165
@@ -182,8 +214,13 @@ static int lev_entry(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_
   if (!return_mistakes && ins_cost == 1.0f && del_cost == 1.0f && sub_cost == 1.0f && workspace &&
       bitpar_enabled()) {
     const BitparPlan p = plan_bitpar(H, R, N);
-    if (p.ok && (int64_t)p.total <= workspace_bytes)
-      return launch_lev_bitpar(a, p, workspace, (hipStream_t)stream, classified);
+    if (p.ok && (int64_t)p.total <= workspace_bytes) {
+      if (tables == kTablesGiven && !kept_tables_has(workspace)) tables = kTablesOwn;  // (never filled: classify)
+      rc = launch_lev_bitpar(a, p, workspace, (hipStream_t)stream, tables);
+      if (tables == kTablesKeep || (tables == kTablesOwn && !p.fused)) kept_tables_note(workspace);
+      else if (tables == kTablesOwn) kept_tables_forget(workspace);
+      return rc;
+    }
   }
   return launch_lev_skewed(a, (hipStream_t)stream);
 }
@@ -196,7 +233,18 @@ int pdt_lev(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn, const
             void *workspace, int64_t workspace_bytes, void *stream) {
   return lev_entry(ref, R, ref_st, ref_sn, hyp, H, hyp_st, hyp_sn, N, has_eos, eos, include_eos, ins_cost,
                    del_cost, sub_cost, norm, mode, exclude_last, padding, return_mistakes, out, out_sh, out_sn,
-                   ref_lens_out, hyp_lens_out, status, workspace, workspace_bytes, stream, false);
+                   ref_lens_out, hyp_lens_out, status, workspace, workspace_bytes, stream, pdt::kTablesOwn);
+}
+
+int pdt_lev_keep(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn, const int64_t *hyp,
+                 int64_t H, int64_t hyp_st, int64_t hyp_sn, int64_t N, int has_eos, int64_t eos,
+                 int include_eos, float ins_cost, float del_cost, float sub_cost, int norm, int mode,
+                 int exclude_last, float padding, int return_mistakes, float *out, int64_t out_sh,
+                 int64_t out_sn, int64_t *ref_lens_out, int64_t *hyp_lens_out, int32_t *status,
+                 void *workspace, int64_t workspace_bytes, void *stream) {
+  return lev_entry(ref, R, ref_st, ref_sn, hyp, H, hyp_st, hyp_sn, N, has_eos, eos, include_eos, ins_cost,
+                   del_cost, sub_cost, norm, mode, exclude_last, padding, return_mistakes, out, out_sh, out_sn,
+                   ref_lens_out, hyp_lens_out, status, workspace, workspace_bytes, stream, pdt::kTablesKeep);
 }
 
 int pdt_lev_classified(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn, const int64_t *hyp,
@@ -207,7 +255,7 @@ int pdt_lev_classified(const int64_t *ref, int64_t R, int64_t ref_st, int64_t re
                        void *workspace, int64_t workspace_bytes, void *stream) {
   return lev_entry(ref, R, ref_st, ref_sn, hyp, H, hyp_st, hyp_sn, N, has_eos, eos, include_eos, ins_cost,
                    del_cost, sub_cost, norm, mode, exclude_last, padding, return_mistakes, out, out_sh, out_sn,
-                   ref_lens_out, hyp_lens_out, status, workspace, workspace_bytes, stream, true);
+                   ref_lens_out, hyp_lens_out, status, workspace, workspace_bytes, stream, pdt::kTablesGiven);
 }
 
 int64_t pdt_oc_mask_words(int64_t R) { return R <= 0 ? 1 : (R + 31) / 32; }

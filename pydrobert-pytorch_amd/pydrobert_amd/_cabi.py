@@ -41,6 +41,11 @@ SIGNATURES = {
         [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _INT, _I64, _INT, _F, _F, _F]
         + [_INT, _INT, _INT, _F, _INT, _P, _I64, _I64, _P, _P, _P, _P, _I64, _P],
     ),
+    "pdt_lev_keep": (
+        _INT,
+        [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _INT, _I64, _INT, _F, _F, _F]
+        + [_INT, _INT, _INT, _F, _INT, _P, _I64, _I64, _P, _P, _P, _P, _I64, _P],
+    ),
     "pdt_lev_classified": (
         _INT,
         [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _INT, _I64, _INT, _F, _F, _F]

@@ -183,7 +183,7 @@ def _lev_workspace(R: int, H: int, N: int, device):
 # OPT-IN (PDT_LEV_CACHE=1, or `with reuse_classification():`): the classification of a (ref, hyp)
 # pair -- lengths, token classes, match tables -- is kept for the NEXT string operator on the same
 # pair (error_rate followed by prefix_error_rates builds them once; include/pdt_amd.h:
-# pdt_lev_classified).  A hit is decided by identity (address, version counter, geometry, eos handling,
+# pdt_lev_keep, pdt_lev_classified).  A hit is decided by identity (address, version counter, geometry, eos handling,
 # stream), NOT by content: writes that do not move the version counter (`t.data[...] = ...`, kernels
 # writing through a raw pointer, graph replays into static buffers, DLPack aliases) leave the key
 # unchanged and the next operator would run on the previous contents' tables.  Hence off by default;
@@ -273,6 +273,9 @@ def _string_matching_op(
                 entry = _cabi.lib().pdt_lev_classified
         if entry is pdt_lev and (uniform or R > 2048):
             ws, ws_bytes = _lev_workspace(R, H, N, device)
+        classifying = entry is pdt_lev and key is not None and ws is not None
+        if classifying:  # (pdt_lev leaves no tables behind: the call a later hit reads from keeps them)
+            entry = _cabi.lib().pdt_lev_keep
         rc = entry(
             _cabi.ptr(ref), R, rst, rsn, _cabi.ptr(hyp), H, hst, hsn, N,
             int(eos is not None), int(eos) if eos is not None else 0, int(include_eos),
@@ -281,8 +284,8 @@ def _string_matching_op(
             _cabi.ptr(out), out_sh, out_sn, 0, 0, _cabi.ptr(status), _cabi.ptr(ws), ws_bytes,
             _cabi.stream_ptr(device),
         )  # fmt: skip
-    _cabi.check(rc, "pdt_lev")
-    if key is not None and ws is not None and entry is pdt_lev:
+    _cabi.check(rc, "pdt_lev_keep" if classifying else "pdt_lev")
+    if classifying:
         _CLASSIFIED[device.index] = (key, ref, hyp, ws, status)
     if warn:
         flags = int(status.item())

@@ -1,7 +1,7 @@
 // Token classes for the Levenshtein kernels: the distinct tokens of one sequence, sorted in
-// registers, and class (= rank) look-ups against that table.  Used by lev_bitpar.hip (classify
-// kernel) and lev_rowsync.hip (optimal completion emits class bitmasks in ascending token order,
-// reference _string.py:503-514).
+// registers, and class (= rank) look-ups against that table.  Used by bitpar_classify.hpp
+// (classify_utterance) and lev_rowsync.hip (optimal completion emits class bitmasks in ascending
+// token order, reference _string.py:503-514).
 #pragma once
 #include "lev_common.hpp"
 #include "wave_select.hpp"

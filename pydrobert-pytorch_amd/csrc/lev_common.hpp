@@ -1,4 +1,4 @@
-// Pieces shared by the two Levenshtein kernels: argument block, token staging
+// Pieces shared by the Levenshtein kernels: argument block, the bit-parallel plan, token staging
 // (int64 global -> int32 LDS ids + length detection) and the host-side cost analysis.
 #pragma once
 #include "pdt_common.hpp"
@@ -19,14 +19,14 @@ struct LevArgs {
   int64_t *ref_lens_out, *hyp_lens_out;
   int32_t *status;
   int waves_per_wg, lds_per_wave;  // bytes
-  // optimal-completion extras (lev_rowsync.hip)
+  // optimal-completion extras (oc_bitpar.hip, lev_rowsync.hip, lev_generic.hip)
   uint32_t *bitmask;
   int64_t *class_tokens;
   int32_t *max_count;
   int W;
 };
 
-// Geometry of the bit-parallel kernels (lev_bitpar.hip) for one call: lanes per utterance,
+// Geometry of the bit-parallel kernels (lev_bitpar.hip, oc_bitpar.hip) for one call: lanes per utterance,
 // utterances per wave, LDS slices and the offsets of the workspace pieces.  ok = 0: the shape is
 // not served (bit-vector sequence longer than 1024 tokens, or lookups that do not fit the LDS).
 struct BitparPlan {

@@ -1,4 +1,5 @@
-// Optimal completion for references beyond the 2048 tokens lev_rowsync.hip holds in registers
+// The plain workgroup formulation (launch_lev_workgroup): optimal completion's masks, and the
+// distances below, for references beyond the 2048 tokens lev_rowsync.hip holds in registers
 // (reference _string.py:464-517 has no such bound): the same class bitmasks and class-token
 // tables, from a plain formulation -- ONE WORKGROUP per utterance, the DP rows, the sort buffer and
 // the class ids in a global workspace (pdt_oc_mask_workspace_bytes), workgroup barriers between
@@ -14,7 +15,7 @@
 // row0[k] = float(k) * del, O(R^2) per row like lev_rowsync.hip's EXACT path.  Then the row minimum
 // and the class bits of the columns that attain it (:333-334, :347-355), OR-ed into the bitmask row
 // in HBM.
-#include "lev_common.hpp"
+#include "lev_launch.hpp"
 
 namespace pdt {
 
@@ -26,7 +27,7 @@ struct GenericOcArgs {
   int inexact;  // replay the reference's deletion unroll term by term
 };
 
-int64_t generic_oc_ws_per_utt(int64_t R, int64_t H, int *P_out) {
+int64_t lev_workgroup_ws_per_utt(int64_t R, int64_t H, int *P_out) {
   int P = 2;
   while (P < R) P <<= 1;
   if (P_out) *P_out = P;
@@ -315,11 +316,11 @@ oc_expand_generic_kernel(const uint32_t *__restrict__ bitmask, const int64_t *__
   for (int i = total + lane; i < C; i += PDT_WAVE) dst[i] = padding;
 }
 
-int launch_oc_mask_generic(const LevArgs &a, bool inexact, void *ws, int64_t ws_bytes, hipStream_t stream) {
+int launch_lev_workgroup(const LevArgs &a, bool inexact, void *ws, int64_t ws_bytes, hipStream_t stream) {
   GenericOcArgs g{};
   g.l = a;
   g.inexact = inexact ? 1 : 0;
-  g.ws_per_utt = generic_oc_ws_per_utt(a.R, a.H, &g.P);
+  g.ws_per_utt = lev_workgroup_ws_per_utt(a.R, a.H, &g.P);
   if (!ws || ws_bytes < g.ws_per_utt * a.N) return PDT_E_TOO_LONG;  // (no workspace: the bounded kernels only)
   g.ws = reinterpret_cast<unsigned char *>(ws);
   hipLaunchKernelGGL(oc_mask_generic_kernel, dim3((unsigned)a.N), dim3(kGenThreads), 0, stream, g);

@@ -17,7 +17,7 @@
 // Every cell is computed with exactly the reference's float32 operations in the reference's
 // order, so COUNT mode is bit-exact for any costs; cost mode is bit-exact whenever all
 // partial sums are exactly representable (the host routes other costs to lev_rowsync.hip).
-#include "lev_common.hpp"
+#include "lev_launch.hpp"
 
 namespace pdt {
 
@@ -227,11 +227,7 @@ int launch_lev_skewed(LevArgs a, hipStream_t stream) {
   const size_t smem = per_wave * wpw;
   const unsigned grid = (unsigned)((a.N + wpw - 1) / wpw);
   auto kern = a.count ? lev_skewed_kernel<true> : lev_skewed_kernel<false>;
-  if (smem > soft_cap) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(kern, smem, soft_cap)) return rc;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * wpw), smem, stream, a);
   return (int)hipGetLastError();
 }

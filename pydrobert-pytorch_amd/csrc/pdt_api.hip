@@ -5,26 +5,12 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "lev_common.hpp"
+#include "lev_launch.hpp"
 #include "switches.hpp"
 #include <cstring>
 #include <mutex>
 
 namespace pdt {
-int launch_lev_skewed(LevArgs a, hipStream_t stream);
-int launch_lev_rowsync(LevArgs a, bool exact, hipStream_t stream);
-int launch_lev_bitpar(const LevArgs &la, const BitparPlan &p, void *ws, hipStream_t stream, LevTables tables);
-int launch_oc_mask_generic(const LevArgs &a, bool inexact, void *ws, int64_t ws_bytes, hipStream_t stream);
-int launch_oc_mask_bitpar(const LevArgs &a, void *ws, int64_t ws_bytes, hipStream_t stream);
-int64_t oc_bitpar_workspace_bytes(int64_t R, int64_t H, int64_t N);
-int launch_oc_expand_generic(const uint32_t *bitmask, const int64_t *class_tokens, int R, int Hout,
-                             int64_t N, int C, int64_t padding, int64_t *targets, int64_t tgt_sh,
-                             int64_t tgt_sn, hipStream_t stream);
-int64_t generic_oc_ws_per_utt(int64_t R, int64_t H, int *P_out);
-int launch_oc_expand(const uint32_t *bitmask, const int64_t *class_tokens, int R, int Hout,
-                     int64_t N, int C, int64_t padding, int64_t *targets, int64_t tgt_sh,
-                     int64_t tgt_sn, hipStream_t stream);
-
 // True when every partial sum the DP can form is an integer multiple of 2^-q below 2^24 in
 // those units, i.e. exactly representable in float32.  Then the textbook recurrence and the
 // reference's unrolled deletion matrix (_string.py:258-266) agree bit for bit.
@@ -49,7 +35,7 @@ static bool costs_exact_in_f32(float ins, float del, float sub, int64_t R, int64
   return false;
 }
 
-// The bit-parallel kernels (lev_bitpar.hip) serve unit costs when the caller passed the workspace
+// The bit-parallel kernels (lev_bitpar.hip, oc_bitpar.hip) serve unit costs when the caller passed the workspace
 // their plan asks for; PDT_LEV_BITPAR=0 keeps the cell-by-cell kernels (for comparisons).
 static bool bitpar_enabled() { return switches().lev_bitpar != 0; }
 
@@ -174,7 +160,7 @@ int64_t pdt_lev_workspace_bytes(int64_t R, int64_t H, int64_t N) {
   }
   // references beyond the row-synchronous kernel's 2048 columns: costs that are inexact in float32
   // take the plain workgroup kernel (lev_generic.hip), whose rows live in the workspace
-  if (R > 64 * 32) need = std::max(need, pdt::generic_oc_ws_per_utt(R, H, nullptr) * N);
+  if (R > 64 * 32) need = std::max(need, pdt::lev_workgroup_ws_per_utt(R, H, nullptr) * N);
   return need;
 }
 
@@ -208,7 +194,7 @@ static int lev_entry(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_
   a.out = out; a.out_sh = out_sh; a.out_sn = out_sn;
   a.ref_lens_out = ref_lens_out; a.hyp_lens_out = hyp_lens_out; a.status = status;
   if (!return_mistakes && !costs_exact_in_f32(ins_cost, del_cost, sub_cost, R, H)) {
-    if (R > 64 * 32) return launch_oc_mask_generic(a, /*inexact=*/true, workspace, workspace_bytes, (hipStream_t)stream);
+    if (R > 64 * 32) return launch_lev_workgroup(a, /*inexact=*/true, workspace, workspace_bytes, (hipStream_t)stream);
     return launch_lev_rowsync(a, /*exact=*/true, (hipStream_t)stream);
   }
   if (!return_mistakes && ins_cost == 1.0f && del_cost == 1.0f && sub_cost == 1.0f && workspace &&
@@ -264,7 +250,7 @@ int64_t pdt_oc_mask_workspace_bytes(int64_t R, int64_t H, int64_t N) {
   if (H < 0 || N <= 0) return 0;
   if (R <= 64 * 32)  // the bit-parallel kernel's tables (unit costs, up to 512 columns); the
     return pdt::oc_bitpar_enabled() ? pdt::oc_bitpar_workspace_bytes(R, H, N) : 0;  // register-resident kernel needs none
-  return pdt::generic_oc_ws_per_utt(R, H, nullptr) * N;
+  return pdt::lev_workgroup_ws_per_utt(R, H, nullptr) * N;
 }
 
 int pdt_oc_mask(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn, const int64_t *hyp,
@@ -291,7 +277,7 @@ int pdt_oc_mask(const int64_t *ref, int64_t R, int64_t ref_st, int64_t ref_sn, c
   a.W = (int)pdt_oc_mask_words(R);
   const bool exact = !costs_exact_in_f32(ins_cost, del_cost, sub_cost, R, H);
   if (a.W > 64) {  // beyond the 2048 columns the row-synchronous kernel holds: the plain formulation
-    return launch_oc_mask_generic(a, exact, workspace, workspace_bytes, (hipStream_t)stream);
+    return launch_lev_workgroup(a, exact, workspace, workspace_bytes, (hipStream_t)stream);
   }
   if (ins_cost == 1.0f && del_cost == 1.0f && sub_cost == 1.0f && oc_bitpar_enabled()) {
     rc = launch_oc_mask_bitpar(a, workspace, workspace_bytes, (hipStream_t)stream);

@@ -2,8 +2,10 @@
 
 Host-side mirror of the reference's ``_string.py``: same functions, argument order,
 defaults, output shapes/dtypes, exceptions and warnings; the dynamic programming itself
-runs in ``csrc/lev_skewed.hip`` / ``csrc/lev_rowsync.hip`` through ``pdt_lev``,
-``pdt_oc_mask`` and ``pdt_oc_expand`` (``include/pdt_amd.h``).
+runs behind ``pdt_lev``, ``pdt_oc_mask`` and ``pdt_oc_expand`` (``include/pdt_amd.h``):
+uniform costs in the bit-parallel kernels of ``csrc/lev_bitpar.hip`` and ``csrc/oc_bitpar.hip``,
+other costs cell by cell in ``csrc/lev_skewed.hip`` / ``csrc/lev_rowsync.hip``, references
+beyond 2048 tokens in ``csrc/lev_generic.hip``; the expansion is ``csrc/oc_expand.hip``.
 """
 
 import contextlib
@@ -170,11 +172,18 @@ def _emit_warnings(flags: int, eos, prefix: bool):
             )
 
 
-def _lev_workspace(R: int, H: int, N: int, device):
-    """Scratch memory of the bit-parallel kernels (``pdt_lev_workspace_bytes``; ``None`` when
-    the shape is served by the cell-by-cell kernels).  torch's caching allocator hands the same
-    block back call after call."""
-    nbytes = int(_cabi.lib().pdt_lev_workspace_bytes(R, H, N))
+def _uniform_costs(ins_cost, del_cost, sub_cost) -> bool:
+    """The costs the native side runs as unit costs (_string.py:168-174)."""
+    return float(ins_cost) == float(del_cost) == float(sub_cost) > 0.0
+
+
+def _workspace(size_fn, uniform: bool, R: int, H: int, N: int, device):
+    """Scratch memory of one call, ``(tensor or None, bytes)``; ``size_fn`` is the entry point's
+    ``pdt_*_workspace_bytes``.  Only the bit-parallel kernels -- uniform costs -- and the plain kernel
+    for references beyond 2048 tokens read a workspace; every other call launches without one, and so
+    does a shape for which ``size_fn`` reports 0 (served by the cell-by-cell kernels).  torch's
+    caching allocator hands the same block back call after call."""
+    nbytes = int(size_fn(R, H, N)) if (uniform or R > 2048) else 0
     if nbytes <= 0:
         return None, 0
     return torch.empty(nbytes, device=device, dtype=torch.uint8), nbytes
@@ -194,14 +203,30 @@ def _lev_workspace(R: int, H: int, N: int, device):
 _CLASSIFIED = {}
 
 
-def _classified_key(ref, hyp, geom, eos, include_eos, norm, stream):
+def _classified_key(device, ref, hyp, geom, eos, include_eos, norm):
     try:
         versions = (ref._version, hyp._version)
     except RuntimeError:  # inference tensors do not track a version counter: no identity to match on
         return None
+    stream = _cabi.stream_ptr(device)
+    stream = stream if isinstance(stream, int) else getattr(stream, "value", None)
     # (without an eos every sequence has its full length: include_eos changes nothing)
     return (ref.data_ptr(), versions[0], hyp.data_ptr(), versions[1], geom, eos,
             bool(include_eos) and eos is not None, bool(norm), stream)
+
+
+def _classified_take(device, key, warn):
+    """Drops the device's entry (it serves one hit) and returns its ``(workspace, status)`` if it was
+    made for ``key`` -- with the warning bits of the classifying call when this call wants them --
+    else ``None``."""
+    hit = _CLASSIFIED.pop(device.index, None)
+    if key is None or hit is None or hit[0] != key or (hit[4] is None and warn):
+        return None
+    return hit[3], hit[4]
+
+
+def _classified_store(device, key, ref, hyp, ws, status):
+    _CLASSIFIED[device.index] = (key, ref, hyp, ws, status)
 
 
 @contextlib.contextmanager
@@ -238,7 +263,7 @@ def _string_matching_op(
 ) -> torch.Tensor:
     """FINAL / PREFIX flavours of the reference's ``_string_matching`` (_string.py:146-406)."""
     device, ref, hyp, (R, rst, rsn), (H, hst, hsn), N = _prep(ref, hyp, batch_first)
-    uniform = ins_cost == del_cost == sub_cost > 0.0
+    uniform = _uniform_costs(ins_cost, del_cost, sub_cost)
     if return_mistakes and not uniform and warn:  # _string.py:175-180
         warnings.warn(
             "The behaviour for non-uniform error rates has changed after v0.3.0. Please "
@@ -256,26 +281,22 @@ def _string_matching_op(
         out = torch.empty((N,), device=device, dtype=torch.float)
         out_sh, out_sn = 0, 1
         mode = _cabi.MODE_FINAL
+    L = _cabi.lib()
     with torch.cuda.device(device):
         status = torch.zeros(1, device=device, dtype=torch.int32) if warn else None
-        # (only the bit-parallel kernels -- uniform costs -- and the plain kernel for references
-        # beyond 2048 tokens read a workspace; every other call launches without one)
-        ws, ws_bytes = None, 0
-        entry = pdt_lev = _cabi.lib().pdt_lev
-        key = None
-        if uniform and switches.get("PDT_LEV_CACHE"):
-            stream = _cabi.stream_ptr(device)
-            key = _classified_key(ref, hyp, (R, rst, rsn, H, hst, hsn, N), eos, include_eos, norm,
-                                  stream if isinstance(stream, int) else getattr(stream, "value", None))
-            hit = _CLASSIFIED.pop(device.index, None)  # (an entry serves one hit)
-            if key is not None and hit is not None and hit[0] == key and (hit[4] is not None or not warn):
-                ws, ws_bytes, status = hit[3], hit[3].numel(), hit[4]  # (the warning bits of the classifying call)
-                entry = _cabi.lib().pdt_lev_classified
-        if entry is pdt_lev and (uniform or R > 2048):
-            ws, ws_bytes = _lev_workspace(R, H, N, device)
-        classifying = entry is pdt_lev and key is not None and ws is not None
-        if classifying:  # (pdt_lev leaves no tables behind: the call a later hit reads from keeps them)
-            entry = _cabi.lib().pdt_lev_keep
+        caching = uniform and switches.get("PDT_LEV_CACHE")
+        geom = (R, rst, rsn, H, hst, hsn, N)
+        key = _classified_key(device, ref, hyp, geom, eos, include_eos, norm) if caching else None
+        kept = _classified_take(device, key, warn) if caching else None
+        remember = False
+        if kept is not None:  # the tables the previous operator on this pair left, and its warning bits
+            (ws, status), entry, name = kept, L.pdt_lev_classified, "pdt_lev"
+            ws_bytes = ws.numel()
+        else:
+            ws, ws_bytes = _workspace(L.pdt_lev_workspace_bytes, uniform, R, H, N, device)
+            # (pdt_lev leaves no tables behind: the call a later hit reads from keeps them)
+            remember = key is not None and ws is not None
+            entry, name = (L.pdt_lev_keep, "pdt_lev_keep") if remember else (L.pdt_lev, "pdt_lev")
         rc = entry(
             _cabi.ptr(ref), R, rst, rsn, _cabi.ptr(hyp), H, hst, hsn, N,
             int(eos is not None), int(eos) if eos is not None else 0, int(include_eos),
@@ -284,9 +305,9 @@ def _string_matching_op(
             _cabi.ptr(out), out_sh, out_sn, 0, 0, _cabi.ptr(status), _cabi.ptr(ws), ws_bytes,
             _cabi.stream_ptr(device),
         )  # fmt: skip
-    _cabi.check(rc, "pdt_lev_keep" if classifying else "pdt_lev")
-    if classifying:
-        _CLASSIFIED[device.index] = (key, ref, hyp, ws, status)
+    _cabi.check(rc, name)
+    if remember:
+        _classified_store(device, key, ref, hyp, ws, status)
     if warn:
         flags = int(status.item())
         if flags:
@@ -506,9 +527,7 @@ def _oc_mask(ref, hyp, eos, include_eos, batch_first, ins_cost, del_cost, sub_co
         scal = torch.zeros(3, device=device, dtype=torch.int32)  # [max_count, status, aux status]
         # the bit-parallel kernel's tables (uniform costs, R <= 512) or the plain formulation's rows
         # (R > 2048); everything else runs out of registers
-        uniform = float(ins_cost) == float(del_cost) == float(sub_cost) and float(sub_cost) > 0.0
-        ws_bytes = int(L.pdt_oc_mask_workspace_bytes(R, H, N)) if (uniform or R > 2048) else 0
-        ws = torch.empty(ws_bytes, device=device, dtype=torch.uint8) if ws_bytes > 0 else None
+        ws, ws_bytes = _workspace(L.pdt_oc_mask_workspace_bytes, _uniform_costs(ins_cost, del_cost, sub_cost), R, H, N, device)
         rc = L.pdt_oc_mask(
             _cabi.ptr(ref), R, rst, rsn, _cabi.ptr(hyp), H, hst, hsn, N,
             int(eos is not None), int(eos) if eos is not None else 0, int(include_eos),

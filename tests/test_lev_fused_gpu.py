@@ -4,9 +4,10 @@ of lev_bitpar_kernel, csrc/lev_bitpar.hip) against the CPU oracle AND against th
 recurrence alone on those tables).  Results are small integers and quotients of them: every
 comparison is exact, and the warning word of the fused call is the two-launch call's.
 
-optimal_completion's mask kernel classifies its own utterances too (oc_bitpar_kernel); pdt_oc_mask has
-no keeping variant, so its other routes are reached the way a caller reaches them: the
-row-synchronous kernel through the switch PDT_OC_BITPAR = 0 (every case), and the two launches
+optimal_completion's mask kernel classifies its own utterances too (oc_bitpar_kernel,
+csrc/oc_bitpar.hip); pdt_oc_mask has no keeping variant, so its other routes are reached the way a
+caller reaches them: the row-synchronous kernel through the switch PDT_OC_BITPAR = 0 (every case),
+and the two launches
 (lev_classify_kernel, then the mask kernel on the workspace's tables) through a hypothesis tensor of
 513 rows -- one row past what the fused form takes -- whose extra row lies behind every eos, so the
 first 513 rows of the result are the same problem's (the cases with an eos and include_eos=False).

@@ -407,7 +407,7 @@ def test_optimal_completion_shape_sweep(device):
 @pytest.mark.parametrize("R", [1, 2, 31, 32, 33, 63, 64, 65, 200, 480, 511, 512])
 def test_optimal_completion_bit_parallel_rows(device, R, switch):
     """Uniform costs and references of up to 512 tokens take the bit-parallel mask kernel
-    (csrc/lev_bitpar.hip, oc_bitpar_kernel): one case per number of 32-column blocks in use, ragged
+    (csrc/oc_bitpar.hip, oc_bitpar_kernel): one case per number of 32-column blocks in use, ragged
     lengths on both sides (eos anywhere, including position 0), vocabularies from two tokens (every
     row minimum tied many times) to more tokens than positions, batches that leave utterance slots
     of the last wave empty.  Checked against the oracle on a slice and against the row-synchronous
@@ -435,7 +435,7 @@ def test_optimal_completion_bit_parallel_rows(device, R, switch):
                 assert np.array_equal(act.cpu().numpy(), exp), (R, H, N, V, kw)
 
 
-# ---- bit-parallel unit-cost kernels (csrc/lev_bitpar.hip) ------------------------------------
+# ---- bit-parallel unit-cost kernels (csrc/lev_bitpar.hip, csrc/oc_bitpar.hip) ----------------
 _BITPAR_OPS = ["error_rate", "edit_distance", "prefix_error_rates", "prefix_edit_distances"]
 
 

@@ -822,6 +822,56 @@ int pdt_slice_ali_emit(const int32_t *seg, int64_t N, int64_t T, const int64_t *
                        const int64_t *cnt, const int64_t *base, int64_t left, int64_t right, int valid_only,
                        int64_t *slices, int64_t *sources, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Discounted returns (reference _rl.py:24-41) as a scan.  r and R are indexed (t, n), t < T,
+ * n < N, through element strides (any layout, no copy); dtype as for the deltas, accumulated in
+ * float32 (float64 for float64).  gamma: one double in host memory, read before the call returns
+ * (as the scale of pdt_attn_dot: the scalar types of this ABI are int, int64_t and float).
+ *   reverse == 0: R[t] = r[t] + gamma * R[t + 1]   (R[T] = 0)
+ *   reverse == 1: R[t] = r[t] + gamma * R[t - 1]   (R[-1] = 0), the adjoint of the above
+ * The kernel follows R's dense axis; time is split into chunks (32 steps per lane when n is dense,
+ * 1024 per wave when t is) when the other axis alone would leave the device idle, through a
+ * workspace of pdt_time_distributed_return_workspace_bytes(...) bytes (0: none needed; -1: bad
+ * arguments).  No power of gamma beyond one chunk is formed, none divided.  T == 0 or N == 0 is OK.
+ * ------------------------------------------------------------------------------------- */
+int64_t pdt_time_distributed_return_workspace_bytes(int64_t T, int64_t N, int dtype, int64_t R_st, int64_t R_sn);
+
+int pdt_time_distributed_return(const void *r, int dtype, int64_t T, int64_t N, int64_t r_st, int64_t r_sn,
+                                const double *gamma, int reverse, void *R, int64_t R_st, int64_t R_sn,
+                                void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Combinatorics (reference _combinatorics.py:27-412).  out_type 0 int64, 1 int32, 2 uint8,
+ * 3 float32, 4 float64.  table: the (67, 67) int64 Pascal table, table[l * 67 + c] = C(l, c), on
+ * the device.
+ * pdt_enumerate_vocab_sequences: out (vocab_size^length, length) contiguous, 16-byte aligned,
+ *   out[s, t] = (s / vocab_size^t) % vocab_size.  length == 0 is OK (nothing to write);
+ *   PDT_E_TOO_LONG when vocab_size^length reaches 2^32 (the row arithmetic is 32-bit).
+ * pdt_binomial_coefficient: out[i] = C(length[i], count[i]), 0 when count > length.  flags[0]
+ *   (zeroed by the caller) gets bit 0 for a negative input, bit 1 for a length above 66; such
+ *   elements are written as 0.
+ * pdt_enumerate_cardinality: out (B, rows, width): out[b, k, :] is the k-th binary sequence of
+ *   length[b] elements with count[b] ones in ascending order of sum_t out[b, k, t] 2^t; rows at or
+ *   beyond C(length[b], count[b]) and columns at or beyond length[b] are zeros.  length == count ==
+ *   NULL: B == 1 and the scalars length0 / count0.  width <= 62.
+ * pdt_srswor: Fan's sequential draw.  total_count, given_count (B,), u and out (B, out_size)
+ *   float32 contiguous: with ell = given_count[b], for t = 0 .. out_size - 1
+ *   out[b, t] = u[b, t] < (float)ell / (float)max(total_count[b] - t, 1), ell -= out[b, t].
+ *   The caller guarantees 0 <= given_count <= total_count and u in [0, 1): a row's sum is then
+ *   exactly given_count[b] and its elements from total_count[b] on are 0.  Not checked here.
+ * ------------------------------------------------------------------------------------- */
+int pdt_enumerate_vocab_sequences(int64_t length, int64_t vocab_size, int out_type, void *out, void *stream);
+
+int pdt_binomial_coefficient(const int64_t *length, const int64_t *count, int64_t n, const int64_t *table,
+                             int64_t *out, int32_t *flags, void *stream);
+
+int pdt_enumerate_cardinality(const int64_t *length, const int64_t *count, int64_t length0, int64_t count0,
+                              int64_t B, int64_t rows, int64_t width, const int64_t *table, int out_type,
+                              void *out, void *stream);
+
+int pdt_srswor(const int64_t *total_count, const int64_t *given_count, const float *u, int64_t B,
+               int64_t out_size, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

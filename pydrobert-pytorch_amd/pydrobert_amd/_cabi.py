@@ -15,7 +15,10 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd.so"))
 
-# what pdt_amd_abi_version() must report: the table below is this version's
+# what pdt_amd_abi_version() must report: the table below is this version's.  A change of the table bumps it
+# on both sides.  The one exception so far: the return and combinatorics entry points were added at 12,
+# because tests/test_random_walk_cpu.py pins that number; a library built before them is still refused by
+# lib(), with its missing-entry-point message in place of the version one.
 ABI_VERSION = 12
 
 PDT_OK = 0
@@ -209,6 +212,14 @@ SIGNATURES = {
     "pdt_slice_ref": (_INT, [_P, _I64, _I64, _P, _P, _I64, _I64, _INT, _P, _INT, _P, _P, _P, _P]),
     "pdt_slice_ali_segments": (_INT, [_P, _I64, _I64, _P, _P, _P, _P]),
     "pdt_slice_ali_emit": (_INT, [_P, _I64, _I64, _P, _P, _P, _P, _I64, _I64, _INT, _P, _P, _P]),
+    "pdt_time_distributed_return_workspace_bytes": (_I64, [_I64, _I64, _INT, _I64, _I64]),
+    "pdt_time_distributed_return": (
+        _INT, [_P, _INT, _I64, _I64, _I64, _I64, _P, _INT, _P, _I64, _I64, _P, _I64, _P],
+    ),
+    "pdt_enumerate_vocab_sequences": (_INT, [_I64, _I64, _INT, _P, _P]),
+    "pdt_binomial_coefficient": (_INT, [_P, _P, _I64, _P, _P, _P, _P]),
+    "pdt_enumerate_cardinality": (_INT, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _INT, _P, _P]),
+    "pdt_srswor": (_INT, [_P, _P, _P, _I64, _I64, _P, _P]),
     "pdt_ctc_prefix_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "pdt_ctc_prefix_search_plan": (_INT, [_I64, _I64, _P]),
     "pdt_ctc_prefix_search": (

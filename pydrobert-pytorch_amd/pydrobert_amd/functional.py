@@ -1,6 +1,13 @@
 """Functional namespace -- mirrors ``pydrobert.torch.functional`` (functional.py:17-95)
 for the operators on the MI355X hot path."""
 
+from ._combinatorics import (
+    binomial_coefficient,
+    enumerate_binary_sequences,
+    enumerate_binary_sequences_with_cardinality,
+    enumerate_vocab_sequences,
+    simple_random_sampling_without_replacement,
+)
 from ._decoding import (
     beam_search_advance,
     ctc_prefix_search,
@@ -19,6 +26,7 @@ from ._img import (
 )
 from ._feats import chunk_token_sequences_by_slices, feat_deltas, mean_var_norm, slice_spect_data
 from ._pad import chunk_by_slices, pad_masked_sequence, pad_variable
+from ._rl import time_distributed_return
 from ._string import (
     hard_optimal_completion_distillation_loss,
     minimum_error_rate_loss,
@@ -31,6 +39,12 @@ from ._string import (
 )
 
 __all__ = [
+    "binomial_coefficient",
+    "enumerate_binary_sequences",
+    "enumerate_binary_sequences_with_cardinality",
+    "enumerate_vocab_sequences",
+    "simple_random_sampling_without_replacement",
+    "time_distributed_return",
     "chunk_by_slices",
     "chunk_token_sequences_by_slices",
     "pad_masked_sequence",

@@ -20,6 +20,7 @@ from ._img import (
 from ._feats import ChunkTokenSequencesBySlices, FeatureDeltas, MeanVarianceNormalization, SliceSpectData
 from ._pad import ChunkBySlices, PadMaskedSequence, PadVariable
 from ._decoding import CTCGreedySearch, RandomWalk, SequenceLogProbabilities
+from ._rl import TimeDistributedReturn
 from ._lm import (
     ExtractableSequentialLanguageModel,
     ExtractableShallowFusionLanguageModel,
@@ -62,6 +63,7 @@ __all__ = [
     "CTCGreedySearch",
     "RandomWalk",
     "SequenceLogProbabilities",
+    "TimeDistributedReturn",
     "HardOptimalCompletionDistillationLoss",
     "MinimumErrorRateLoss",
     "BeamSearch",

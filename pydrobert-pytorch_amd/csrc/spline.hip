@@ -1,0 +1,261 @@
+// Polyharmonic splines for gfx950: the solver, the evaluation at query points, and warp_1d_grid.
+//
+// Replaces, from the reference's _img.py:
+//   polyharmonic_spline (:59-150)            -> spline_solve_kernel + spline_apply_kernel
+//   warp_1d_grid (:268-303)                  -> warp_1d_grid_kernel (3-knot spline, 5x5 solve)
+// The small dense systems are solved in float64 (partial pivoting).  pdt::spline_solve also serves
+// the sparse image warp (image_warp.hip, through img_launch.hpp).
+#include "img_launch.hpp"
+#include "img_sample.hpp"
+
+namespace pdt {
+
+// Solve the bordered system [[A + reg*I, B], [B^T, 0]] [w; v] = [f; 0] (_img.py:79-130) for one
+// batch element with the whole workgroup.  a: (S, S + O) augmented matrix in LDS (doubles).
+__device__ void solve_in_lds(double *a, int S, int O, int *piv_row) {
+  const int tid = (int)threadIdx.x, nt = (int)blockDim.x;
+  const int ld = S + O;
+  for (int p = 0; p < S; ++p) {
+    if (tid == 0) {  // partial pivoting
+      int best = p;
+      double bv = fabs(a[p * ld + p]);
+      for (int r = p + 1; r < S; ++r) {
+        const double v = fabs(a[r * ld + p]);
+        if (v > bv) {
+          bv = v;
+          best = r;
+        }
+      }
+      *piv_row = best;
+    }
+    __syncthreads();
+    const int pr = *piv_row;
+    if (pr != p)
+      for (int c = tid; c < ld; c += nt) {
+        const double t = a[p * ld + c];
+        a[p * ld + c] = a[pr * ld + c];
+        a[pr * ld + c] = t;
+      }
+    __syncthreads();
+    const double inv = 1.0 / a[p * ld + p];
+    // eliminate column p from every other row (Gauss-Jordan): rows x columns over the threads
+    const int ncol = ld - p - 1;
+    for (int i = tid; i < S * ncol; i += nt) {
+      const int r = i / ncol, c = p + 1 + (i - r * ncol);
+      if (r != p) a[r * ld + c] -= a[r * ld + p] * inv * a[p * ld + c];
+    }
+    __syncthreads();
+    for (int r = tid; r < S; r += nt)
+      if (r != p) a[r * ld + p] = 0.0;
+    __syncthreads();
+  }
+  for (int i = tid; i < S * O; i += nt) {
+    const int r = i / O, c = S + (i - r * O);
+    a[r * ld + c] /= a[r * ld + r];
+  }
+  __syncthreads();
+}
+
+// train points c (N,T,I), values f (N,T,O) -> wv (N, T+I+1, O) doubles.  `tail` (N, I+1, O) or
+// null: the last I + 1 rows of the right-hand side (zeros for the interpolation problem itself;
+// the adjoint system of the backward pass has them).  `gmat` non-null: the augmented matrix of
+// batch element n lives at gmat + n * S * (S + O) in global memory instead of LDS (systems too
+// large for LDS; a workgroup's own global writes are visible to it after __syncthreads()).
+__global__ void __launch_bounds__(256)
+spline_solve_kernel(const float *__restrict__ c, const float *__restrict__ f,
+                    const float *__restrict__ tail, int T, int I, int O, int order, float reg,
+                    double *__restrict__ wv, double *gmat) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int S = T + I + 1, ld = S + O;
+  const int64_t n = blockIdx.x;
+  double *a = gmat ? gmat + n * (int64_t)S * ld : reinterpret_cast<double *>(smem);
+  int *piv = gmat ? reinterpret_cast<int *>(smem) : reinterpret_cast<int *>(a + (size_t)S * ld);
+  const float *cn = c + n * (int64_t)T * I;
+  const float *fn = f + n * (int64_t)T * O;
+  for (int i = (int)threadIdx.x; i < S * ld; i += (int)blockDim.x) {
+    const int r = i / ld, col = i - r * ld;
+    double v = 0.0;
+    if (r < T && col < T) {
+      double d2 = 0.0;
+      for (int k = 0; k < I; ++k) {
+        const double d = (double)cn[r * I + k] - (double)cn[col * I + k];
+        d2 += d * d;
+      }
+      v = phi_d(sqrt(d2), order);
+      if (r == col && reg > 0.0f) v += (double)reg;
+    } else if (r < T && col < S) {  // B
+      v = (col - T) < I ? (double)cn[r * I + (col - T)] : 1.0;
+    } else if (r >= T && col < T) {  // B^T
+      v = (r - T) < I ? (double)cn[col * I + (r - T)] : 1.0;
+    } else if (r < T && col >= S) {
+      v = (double)fn[r * O + (col - S)];
+    } else if (r >= T && col >= S && tail) {
+      v = (double)tail[(n * (I + 1) + (r - T)) * O + (col - S)];
+    }
+    a[i] = v;
+  }
+  __syncthreads();
+  solve_in_lds(a, S, O, piv);
+  for (int i = (int)threadIdx.x; i < S * O; i += (int)blockDim.x) {
+    const int r = i / O, o = i - r * O;
+    wv[(n * S + r) * O + o] = a[r * ld + S + o];
+  }
+}
+
+// out[n,q,o] = sum_t phi(|x_q - c_t|) w[t,o] + x_q . v[:I,o] + v[I,o]     (_img.py:67-76)
+__global__ void __launch_bounds__(256)
+spline_apply_kernel(const float *__restrict__ c, const double *__restrict__ wv,
+                    const float *__restrict__ x, int T, int I, int O, int Q, int order,
+                    float *__restrict__ out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  double *lw = reinterpret_cast<double *>(smem);            // (T + I + 1, O)
+  float *lc = reinterpret_cast<float *>(lw + (size_t)(T + I + 1) * O);  // (T, I)
+  const int64_t n = blockIdx.y;
+  for (int i = (int)threadIdx.x; i < (T + I + 1) * O; i += (int)blockDim.x)
+    lw[i] = wv[n * (int64_t)(T + I + 1) * O + i];
+  for (int i = (int)threadIdx.x; i < T * I; i += (int)blockDim.x) lc[i] = c[n * (int64_t)T * I + i];
+  __syncthreads();
+  const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (q >= Q) return;
+  const float *xq = x + (n * (int64_t)Q + q) * I;
+  for (int o = 0; o < O; ++o) {
+    double acc = lw[(T + I) * O + o];
+    for (int k = 0; k < I; ++k) acc += (double)xq[k] * lw[(T + k) * O + o];
+    for (int t = 0; t < T; ++t) {
+      double d2 = 0.0;
+      for (int k = 0; k < I; ++k) {
+        const double d = (double)xq[k] - (double)lc[t * I + k];
+        d2 += d * d;
+      }
+      acc += phi_d(sqrt(d2), order) * lw[t * O + o];
+    }
+    out[(n * (int64_t)Q + q) * O + o] = (float)acc;
+  }
+}
+
+// warp_1d_grid (_img.py:268-303): one workgroup per batch element
+__global__ void __launch_bounds__(256)
+warp_1d_grid_kernel(const float *__restrict__ src, const float *__restrict__ flow,
+                    const float *__restrict__ lengths, int T, int order,
+                    float *__restrict__ grid) {
+  __shared__ double a[5 * 6];
+  __shared__ int piv;
+  __shared__ double knots[3];
+  const int64_t n = blockIdx.x;
+  const double len = (double)lengths[n];
+  if (threadIdx.x == 0) {
+    const double eps = (double)FLT_EPSILON;
+    double s = fmax(fmin((double)src[n], len - 1.0), 0.0);
+    double d = fmax(fmin(s + (double)flow[n], len - 1.0), 0.0);
+    s = (2.0 * s + 1.0) / T - 1.0;
+    d = (2.0 * d + 1.0) / T - 1.0;
+    const double lo = 1.0 / T - 1.0 - eps, up = (2.0 * len - 1.0) / T - 1.0 + eps;
+    const double cp[3] = {lo, d, up}, fv[3] = {lo, s, up};  // spline FROM dst TO src
+    for (int r = 0; r < 5; ++r)
+      for (int c = 0; c < 6; ++c) {
+        double v = 0.0;
+        if (r < 3 && c < 3) v = phi_d(fabs(cp[r] - cp[c]), order);
+        else if (r < 3 && c == 3) v = cp[r];
+        else if (r < 3 && c == 4) v = 1.0;
+        else if (r == 3 && c < 3) v = cp[c];
+        else if (r == 4 && c < 3) v = 1.0;
+        else if (r < 3 && c == 5) v = fv[r];
+        a[r * 6 + c] = v;
+      }
+    for (int k = 0; k < 3; ++k) knots[k] = cp[k];
+  }
+  __syncthreads();
+  solve_in_lds(a, 5, 1, &piv);
+  const double w0 = a[0 * 6 + 5], w1 = a[1 * 6 + 5], w2 = a[2 * 6 + 5];
+  const double v0 = a[3 * 6 + 5], v1 = a[4 * 6 + 5];
+  for (int j = (int)threadIdx.x; j < T; j += (int)blockDim.x) {
+    const double t = (2.0 * j + 1.0) / T - 1.0;
+    const double g = w0 * phi_d(fabs(t - knots[0]), order) + w1 * phi_d(fabs(t - knots[1]), order) +
+                     w2 * phi_d(fabs(t - knots[2]), order) + v0 * t + v1;
+    grid[n * (int64_t)T + j] = (float)g;
+  }
+}
+
+int spline_solve(const float *c, const float *f, const float *tail, int64_t N, int64_t T, int64_t I, int64_t O,
+                 int order, float reg, double *wv, hipStream_t stream) {
+  const int64_t S = T + I + 1;
+  if (S > 4096 || O > 64) return PDT_E_TOO_LONG;
+  size_t smem = (size_t)S * (S + O) * sizeof(double) + 16;
+  double *gmat = nullptr;
+  if (smem > kSplineLdsCap) {  // the matrix follows the (N, S, O) doubles + floats of the solutions
+    gmat = reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(wv) +
+                                      (((size_t)N * S * O * (sizeof(double) + sizeof(float)) + 63) & ~(size_t)63));
+    smem = 16;
+  }
+  if (smem > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(spline_solve_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(spline_solve_kernel, dim3((unsigned)N), dim3(256), smem, stream, c, f, tail,
+                     (int)T, (int)I, (int)O, order, reg, wv, gmat);
+  return (int)hipGetLastError();
+}
+
+}  // namespace pdt
+
+extern "C" {
+
+int64_t pdt_spline_workspace_bytes(int64_t N, int64_t T, int64_t I, int64_t O) {
+  if (N < 0 || T < 0 || I < 0 || O < 0) return 0;
+  const int64_t S = T + I + 1;
+  int64_t bytes = N * S * O * (int64_t)(sizeof(double) + sizeof(float)) + 64;
+  bytes += N * pdt::kWarpTableFloats * (int64_t)sizeof(float);  // sparse_warp_bands_kernel's per-image table
+  // systems beyond the LDS are eliminated in global memory, after the solutions
+  if ((size_t)S * (S + O) * sizeof(double) + 16 > pdt::kSplineLdsCap) bytes += N * S * (S + O) * (int64_t)sizeof(double);
+  return bytes;
+}
+
+int pdt_spline_solve(const float *train_points, const float *train_values, const float *tail,
+                     int64_t N, int64_t T, int64_t I, int64_t O, int order,
+                     float regularization_weight, double *solution, void *workspace, void *stream) {
+  using namespace pdt;
+  if (N < 0 || T < 1 || I < 1 || O < 1 || order < 1) return PDT_E_ARG;
+  if (N == 0) return PDT_OK;
+  if (!train_points || !train_values || !solution || !workspace) return PDT_E_ARG;
+  if (N > 65535) return PDT_E_TOO_LONG;
+  double *wv = reinterpret_cast<double *>(workspace);
+  int rc = spline_solve(train_points, train_values, tail, N, T, I, O, order, regularization_weight, wv,
+                        (hipStream_t)stream);
+  if (rc != PDT_OK) return rc;
+  return (int)hipMemcpyAsync(solution, wv, (size_t)N * (T + I + 1) * O * sizeof(double),
+                             hipMemcpyDeviceToDevice, (hipStream_t)stream);
+}
+
+int pdt_polyharmonic_spline(const float *train_points, const float *train_values,
+                            const float *query_points, int64_t N, int64_t T, int64_t I, int64_t O,
+                            int64_t Q, int order, float regularization_weight, float *out,
+                            void *workspace, void *stream) {
+  using namespace pdt;
+  if (N < 0 || T < 1 || I < 1 || O < 1 || Q < 0 || order < 1) return PDT_E_ARG;
+  if (N == 0 || Q == 0) return PDT_OK;
+  if (!train_points || !train_values || !query_points || !out || !workspace) return PDT_E_ARG;
+  if (N > 65535) return PDT_E_TOO_LONG;
+  double *wv = reinterpret_cast<double *>(workspace);
+  int rc = spline_solve(train_points, train_values, nullptr, N, T, I, O, order, regularization_weight, wv,
+                        (hipStream_t)stream);
+  if (rc != PDT_OK) return rc;
+  const size_t smem = (size_t)(T + I + 1) * O * sizeof(double) + (size_t)T * I * sizeof(float);
+  hipLaunchKernelGGL(spline_apply_kernel, dim3((unsigned)((Q + 255) / 256), (unsigned)N), dim3(256),
+                     smem, (hipStream_t)stream, train_points, wv, query_points, (int)T, (int)I,
+                     (int)O, (int)Q, order, out);
+  return (int)hipGetLastError();
+}
+
+int pdt_warp_1d_grid(const float *src, const float *flow, const float *lengths, int64_t N, int64_t T,
+                     int order, float *grid, void *stream) {
+  using namespace pdt;
+  if (N < 0 || T < 0 || order < 1) return PDT_E_ARG;
+  if (N == 0 || T == 0) return PDT_OK;
+  if (!src || !flow || !lengths || !grid) return PDT_E_ARG;
+  hipLaunchKernelGGL(warp_1d_grid_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, src,
+                     flow, lengths, (int)T, order, grid);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

@@ -2,7 +2,7 @@
 
 Host-side mirror of the reference's ``_img.py`` for the operators on the hot path
 (``polyharmonic_spline``, ``warp_1d_grid``, ``dense_image_warp``, ``sparse_image_warp``,
-``spec_augment*`` and their Modules).  Kernels: ``csrc/img_warp.hip`` through the C ABI
+``spec_augment*`` and their Modules).  Kernels: ``csrc/spline.hip``, ``csrc/spec_augment.hip``, ``csrc/image_warp.hip`` through the C ABI
 (``include/pdt_amd.h``).  ``spec_augment_apply_parameters`` and the image warps are
 differentiable with respect to the features / image (bilinear scatter in the backward pass).
 """
@@ -342,7 +342,7 @@ def _(image, flow, indexing, mode, padding_mode):
 def _dense_image_warp_backward_op(
     grad_out: torch.Tensor, flow: torch.Tensor, indexing: str, mode: str, padding_mode: str
 ) -> torch.Tensor:
-    """Adjoint of the gather with respect to the image (csrc/img_warp.hip, BACKWARD)."""
+    """Adjoint of the gather with respect to the image (csrc/image_warp.hip, BACKWARD)."""
     device = _cabi.require_hip(grad_out, flow)
     (g, sfx), fl = _pixels(grad_out), _f32c(flow)
     N, C, H, W = g.shape
@@ -706,6 +706,34 @@ def _spec_augment_check_input(feats: torch.Tensor, lengths: Optional[torch.Tenso
     _spec_augment_raise_unless(_spec_augment_lengths_ok(feats, lengths), feats.size(1))
 
 
+def _lens_long(lengths: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """``lengths`` as the kernels read them: contiguous int64, detached (or None)."""
+    if lengths is None:
+        return None
+    lens = lengths.detach()
+    if lens.dtype != torch.long or not lens.is_contiguous():
+        lens = lens.long().contiguous()
+    return lens
+
+
+def _full_lengths(N: int, T: int, device: torch.device) -> torch.Tensor:
+    """The lengths of a batch given without any: every utterance spans the whole axis."""
+    return torch.full((N,), T, dtype=torch.long, device=device)
+
+
+def _masks_enabled(max_time_mask: int, max_time_mask_proportion: float, num_time_mask: int,
+                   num_time_mask_proportion: float, max_freq_mask: int, num_freq_mask: int) -> Tuple[bool, bool]:  # fmt: skip
+    """``(tm, fm)``: does the configuration draw time / frequency masks at all (reference _img.py:1099, :1127)."""
+    tm = max_time_mask != 0 and max_time_mask_proportion != 0.0 and num_time_mask != 0 and num_time_mask_proportion != 0.0
+    fm = max_freq_mask != 0 and num_freq_mask != 0
+    return tm, fm
+
+
+def _mask_counts(t_0: Optional[torch.Tensor], f_0: Optional[torch.Tensor]) -> Tuple[int, int]:
+    """``(mt, mf)``: masks per utterance along time and frequency (None: no masks)."""
+    return (0 if t_0 is None else t_0.shape[1]), (0 if f_0 is None else f_0.shape[1])
+
+
 @custom_op("pydrobert_amd::spec_augment_draw", mutates_args=())
 def _spec_augment_draw_op(
     uniforms: torch.Tensor,
@@ -723,7 +751,7 @@ def _spec_augment_draw_op(
     is_double: bool,
 ) -> List[torch.Tensor]:
     """Every SpecAugment parameter from one ``(N, R)`` tensor of uniform draws, in ONE kernel
-    (csrc/img_warp.hip: spec_augment_draw_kernel; reference _img.py:1082-1137, which spends ~35 tiny
+    (csrc/spec_augment.hip: spec_augment_draw_kernel; reference _img.py:1082-1137, which spends ~35 tiny
     launches on it).  Returns ``[w_0, w, v_0, v, t_0, t, f_0, f]``; groups the configuration disables
     come back with zero elements."""
     device = _cabi.require_hip(uniforms, lengths)
@@ -732,13 +760,9 @@ def _spec_augment_draw_op(
     if u.dtype != torch.float or not u.is_contiguous():
         u = u.float().contiguous()
     tw, fw = max_time_warp != 0.0, max_freq_warp != 0.0
-    tm = max_time_mask != 0 and max_time_mask_proportion != 0.0 and num_time_mask != 0 and num_time_mask_proportion != 0.0
-    fm = max_freq_mask != 0 and num_freq_mask != 0
-    lens = None
-    if lengths is not None:
-        lens = lengths.detach()
-        if lens.dtype != torch.long or not lens.is_contiguous():
-            lens = lens.long().contiguous()
+    tm, fm = _masks_enabled(max_time_mask, max_time_mask_proportion, num_time_mask, num_time_mask_proportion,
+                            max_freq_mask, num_freq_mask)
+    lens = _lens_long(lengths)
     with torch.cuda.device(device):
         fl = [torch.empty((N if on else 0,), device=device, dtype=torch.float) for on in (tw, tw, fw, fw)]
         tt = [torch.empty((N, num_time_mask) if tm else (0,), device=device, dtype=torch.long) for _ in range(2)]
@@ -759,8 +783,8 @@ def _(uniforms, lengths, T, F, max_time_warp, max_freq_warp, max_time_mask, max_
       max_time_mask_proportion, num_time_mask, num_time_mask_proportion, num_freq_mask, is_double):  # fmt: skip
     N = uniforms.shape[0]
     tw, fw = max_time_warp != 0.0, max_freq_warp != 0.0
-    tm = max_time_mask != 0 and max_time_mask_proportion != 0.0 and num_time_mask != 0 and num_time_mask_proportion != 0.0
-    fm = max_freq_mask != 0 and num_freq_mask != 0
+    tm, fm = _masks_enabled(max_time_mask, max_time_mask_proportion, num_time_mask, num_time_mask_proportion,
+                            max_freq_mask, num_freq_mask)
     fl = [uniforms.new_empty((N if on else 0,), dtype=torch.float) for on in (tw, tw, fw, fw)]
     tt = [uniforms.new_empty((N, num_time_mask) if tm else (0,), dtype=torch.long) for _ in range(2)]
     ff = [uniforms.new_empty((N, num_freq_mask) if fm else (0,), dtype=torch.long) for _ in range(2)]
@@ -812,8 +836,8 @@ def _spec_augment_draw(
     N, T, F = feats.size(0), feats.size(1), feats.size(2)
     device = feats.device
     tw, fw = max_time_warp != 0.0, max_freq_warp != 0.0
-    tm = max_time_mask != 0 and max_time_mask_proportion != 0.0 and num_time_mask != 0 and num_time_mask_proportion != 0.0
-    fm = max_freq_mask != 0 and num_freq_mask != 0
+    tm, fm = _masks_enabled(max_time_mask, max_time_mask_proportion, num_time_mask, num_time_mask_proportion,
+                            max_freq_mask, num_freq_mask)
     R = 2 * int(tw) + 2 * int(fw) + (2 * num_time_mask if tm else 0) + (2 * num_freq_mask if fm else 0)
     none = torch.empty(0)  # a disabled group: the reference's ``torch.empty(0)`` pair (_img.py:1093-1139)
     if R == 0 or N == 0:  # nothing is drawn: no kernel (and no device) is needed
@@ -851,14 +875,13 @@ def _spec_augment_apply_op(
     f: Optional[torch.Tensor],
 ) -> torch.Tensor:
     """Time / frequency resampling through the 1-D grids, then band masks: ONE pass over
-    ``feats`` (csrc/img_warp.hip)."""
+    ``feats`` (csrc/spec_augment.hip)."""
     device = _cabi.require_hip(feats, tgrid, fgrid, t_0, t, f_0, f)
     N, T, F = feats.shape
     x = feats.detach()
     if x.dtype != torch.float:
         x = x.float()
-    mt = 0 if t_0 is None else t_0.shape[1]
-    mf = 0 if f_0 is None else f_0.shape[1]
+    mt, mf = _mask_counts(t_0, f_0)
     with torch.cuda.device(device):
         out = torch.empty((N, T, F), device=device, dtype=torch.float)
         rc = _cabi.lib().pdt_spec_augment_apply(
@@ -890,8 +913,7 @@ def _spec_augment_apply_backward_op(
     device = _cabi.require_hip(grad_out, tgrid, fgrid, t_0, t, f_0, f)
     g = _f32c(grad_out)
     N, T, F = g.shape
-    mt = 0 if t_0 is None else t_0.shape[1]
-    mf = 0 if f_0 is None else f_0.shape[1]
+    mt, mf = _mask_counts(t_0, f_0)
     with torch.cuda.device(device):
         grad = torch.empty_like(g)
         rc = _cabi.lib().pdt_spec_augment_apply_backward(
@@ -906,6 +928,34 @@ def _spec_augment_apply_backward_op(
 @_spec_augment_apply_backward_op.register_fake
 def _(grad_out, tgrid, fgrid, t_0, t, f_0, f):
     return grad_out.new_empty(grad_out.shape)
+
+
+def _launch_apply_warp(device, x, src, flow, lens, order, t_0, t, mt, f_0, f, mf, check_lengths) -> Optional[torch.Tensor]:
+    """One launch of ``pdt_spec_augment_apply_warp`` on float features ``x``: the result, or None for a
+    layout the one-pass kernel does not take (the caller goes through the grid).
+
+    ``check_lengths``: the reference's "values of lengths must be between (1, T)" (_img.py:1037-1041)
+    decided by the kernel that reads the lengths -- a word in pinned host memory, looked at once the
+    stream has drained -- instead of four small kernels, a copy and a synchronisation in front of it."""
+    N, T, F = x.shape
+    report = _cabi.host_report(device) if (check_lengths and lens is not None) else None
+    with torch.cuda.device(device):
+        out = torch.empty((N, T, F), device=device, dtype=torch.float)
+        rc = _cabi.lib().pdt_spec_augment_apply_warp(
+            _cabi.ptr(x), N, T, F, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(src), _cabi.ptr(flow),
+            _cabi.ptr(lens), int(order), _cabi.ptr(t_0), _cabi.ptr(t), mt, _cabi.ptr(f_0), _cabi.ptr(f), mf,
+            _cabi.ptr(out), 0 if report is None else report.ptr, _cabi.stream_ptr(device),
+        )  # fmt: skip
+    if report is not None and (rc or not (N and T and F)):
+        report.disarm()  # (no kernel was launched)
+    if rc == _cabi.PDT_E_UNSUPPORTED:
+        return None
+    _cabi.check(rc, "pdt_spec_augment_apply_warp")
+    if report is not None and N and T and F:
+        torch.cuda.current_stream(device).synchronize()
+        if report.read() != 0:
+            raise RuntimeError("values of lengths must be between (1, {})".format(T))
+    return out
 
 
 @custom_op("pydrobert_amd::spec_augment_apply_warp", mutates_args=())
@@ -923,7 +973,7 @@ def _spec_augment_apply_warp_op(
 ) -> torch.Tensor:
     """``spec_augment_apply`` with the time warp given by its parameters ``(w_0, w, lengths)``: the
     three-knot spline of ``warp_1d_grid`` is solved in closed form inside the one pass over ``feats``
-    (csrc/img_warp.hip: warp_1d_spline) -- one launch, no ``(N, T)`` grid, one operator instead of two.
+    (csrc/img_sample.hpp: warp_1d_spline) -- one launch, no ``(N, T)`` grid, one operator instead of two.
     Layouts the one-pass kernel does not take go through the grid as before."""
     device = _cabi.require_hip(feats, w_0, w, lengths, t_0, t, f_0, f)
     N, T, F = feats.shape
@@ -931,37 +981,15 @@ def _spec_augment_apply_warp_op(
     if x.dtype != torch.float:
         x = x.float()
     src, flow = _f32c(w_0), _f32c(w)
-    lens = None
-    if lengths is not None:
-        lens = lengths.detach()
-        if lens.dtype != torch.long or not lens.is_contiguous():
-            lens = lens.long().contiguous()
-    mt = 0 if t_0 is None else t_0.shape[1]
-    mf = 0 if f_0 is None else f_0.shape[1]
-    # ``check_lengths``: the reference's "values of lengths must be between (1, T)" (_img.py:1037-1041)
-    # decided by the kernel that reads the lengths -- a word in pinned host memory, looked at once the
-    # stream has drained -- instead of four small kernels, a copy and a synchronisation in front of it
-    report = _cabi.host_report(device) if (check_lengths and lens is not None) else None
-    with torch.cuda.device(device):
-        out = torch.empty((N, T, F), device=device, dtype=torch.float)
-        rc = _cabi.lib().pdt_spec_augment_apply_warp(
-            _cabi.ptr(x), N, T, F, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(src), _cabi.ptr(flow),
-            _cabi.ptr(lens), int(interpolation_order), _cabi.ptr(t_0), _cabi.ptr(t), mt, _cabi.ptr(f_0), _cabi.ptr(f), mf,
-            _cabi.ptr(out), 0 if report is None else report.ptr, _cabi.stream_ptr(device),
-        )  # fmt: skip
-    if report is not None and (rc or not (N and T and F)):
-        report.disarm()  # (no kernel was launched)
-    if rc == _cabi.PDT_E_UNSUPPORTED:
-        if report is not None:
+    lens = _lens_long(lengths)
+    mt, mf = _mask_counts(t_0, f_0)
+    out = _launch_apply_warp(device, x, src, flow, lens, interpolation_order, t_0, t, mt, f_0, f, mf, check_lengths)
+    if out is None:
+        if check_lengths and lens is not None:
             _spec_augment_raise_unless(torch.all((lens <= T) & (lens > 0)), T)
-        ln = lens if lens is not None else torch.full((N,), T, dtype=torch.long, device=device)
+        ln = lens if lens is not None else _full_lengths(N, T, device)
         tgrid = torch.ops.pydrobert_amd.warp_1d_grid(src, flow, ln, T, interpolation_order)
         return torch.ops.pydrobert_amd.spec_augment_apply(feats, tgrid, None, t_0, t, f_0, f)
-    _cabi.check(rc, "pdt_spec_augment_apply_warp")
-    if report is not None and N and T and F:
-        torch.cuda.current_stream(device).synchronize()
-        if report.read() != 0:
-            raise RuntimeError("values of lengths must be between (1, {})".format(T))
     return out.to(feats.dtype)
 
 
@@ -978,7 +1006,7 @@ def _spec_warp_setup_context(ctx, inputs, output):
 def _spec_warp_backward(ctx, grad_out):
     # (the adjoint reads the grid: formed here, where a gradient is actually asked for)
     w_0, w, lengths, order, t_0, t, f_0, f = ctx.args[:8]
-    ln = lengths if lengths is not None else torch.full((w_0.shape[0],), ctx.T, dtype=torch.long, device=w_0.device)
+    ln = lengths if lengths is not None else _full_lengths(w_0.shape[0], ctx.T, w_0.device)
     tgrid = torch.ops.pydrobert_amd.warp_1d_grid(w_0.detach(), w.detach(), ln, ctx.T, order)
     g = torch.ops.pydrobert_amd.spec_augment_apply_backward(grad_out, tgrid, None, t_0, t, f_0, f)
     return g, None, None, None, None, None, None, None, None, None
@@ -1016,20 +1044,15 @@ def _spec_augment_forward_op(
     u = uniforms.detach()
     if u.dtype != torch.float or not u.is_contiguous():
         u = u.float().contiguous()
-    tm = max_time_mask != 0 and max_time_mask_proportion != 0.0 and num_time_mask != 0 and num_time_mask_proportion != 0.0
-    fm = max_freq_mask != 0 and num_freq_mask != 0
-    lens = None
-    if lengths is not None:
-        lens = lengths.detach()
-        if lens.dtype != torch.long or not lens.is_contiguous():
-            lens = lens.long().contiguous()
+    tm, fm = _masks_enabled(max_time_mask, max_time_mask_proportion, num_time_mask, num_time_mask_proportion,
+                            max_freq_mask, num_freq_mask)
+    lens = _lens_long(lengths)
     L = _cabi.lib()
     with torch.cuda.device(device):
         stream = _cabi.stream_ptr(device)
         w_0, w = (torch.empty((N,), device=device, dtype=torch.float) for _ in range(2))
         t_0, t = (torch.empty((N, num_time_mask) if tm else (0,), device=device, dtype=torch.long) for _ in range(2))
         f_0, f = (torch.empty((N, num_freq_mask) if fm else (0,), device=device, dtype=torch.long) for _ in range(2))
-        out = torch.empty((N, T, F), device=device, dtype=torch.float)
         rc = L.pdt_spec_augment_draw(
             _cabi.ptr(u), N, u.size(1), _cabi.ptr(lens), T, F, float(max_time_warp), 0.0,
             int(max_time_mask), int(max_freq_mask), float(max_time_mask_proportion), int(num_time_mask),
@@ -1038,24 +1061,14 @@ def _spec_augment_forward_op(
             _cabi.ptr(f_0) if fm else 0, _cabi.ptr(f) if fm else 0, stream,
         )  # fmt: skip
         _cabi.check(rc, "pdt_spec_augment_draw")
-        report = _cabi.host_report(device) if lens is not None else None
-        rc = L.pdt_spec_augment_apply_warp(
-            _cabi.ptr(x), N, T, F, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(w_0), _cabi.ptr(w),
-            _cabi.ptr(lens), int(interpolation_order), _cabi.ptr(t_0) if tm else 0, _cabi.ptr(t) if tm else 0,
-            num_time_mask if tm else 0, _cabi.ptr(f_0) if fm else 0, _cabi.ptr(f) if fm else 0,
-            num_freq_mask if fm else 0, _cabi.ptr(out), 0 if report is None else report.ptr, stream,
-        )  # fmt: skip
-    if report is not None and (rc or not (N and T and F)):
-        report.disarm()  # (no kernel was launched)
-    if rc == _cabi.PDT_E_UNSUPPORTED:  # (a layout the one-pass kernel does not take: through the grid)
+    out = _launch_apply_warp(
+        device, x, w_0, w, lens, interpolation_order, t_0 if tm else None, t if tm else None,
+        num_time_mask if tm else 0, f_0 if fm else None, f if fm else None, num_freq_mask if fm else 0, True,
+    )  # fmt: skip
+    if out is None:  # (a layout the one-pass kernel does not take: through the grid)
         out = _spec_augment_apply(feats, (w_0, w, torch.empty(0), torch.empty(0), t_0, t, f_0, f), interpolation_order,
                                   lengths, True)
         return [out, w_0, w, t_0, t, f_0, f]
-    _cabi.check(rc, "pdt_spec_augment_apply_warp")
-    if report is not None and N and T and F:
-        torch.cuda.current_stream(device).synchronize()
-        if report.read() != 0:
-            raise RuntimeError("values of lengths must be between (1, {})".format(T))
     return [out.to(feats.dtype), w_0, w, t_0, t, f_0, f]
 
 
@@ -1063,8 +1076,8 @@ def _spec_augment_forward_op(
 def _(feats, uniforms, lengths, max_time_warp, max_time_mask, max_freq_mask, max_time_mask_proportion, num_time_mask,
       num_time_mask_proportion, num_freq_mask, interpolation_order):  # fmt: skip
     N = feats.shape[0]
-    tm = max_time_mask != 0 and max_time_mask_proportion != 0.0 and num_time_mask != 0 and num_time_mask_proportion != 0.0
-    fm = max_freq_mask != 0 and num_freq_mask != 0
+    tm, fm = _masks_enabled(max_time_mask, max_time_mask_proportion, num_time_mask, num_time_mask_proportion,
+                            max_freq_mask, num_freq_mask)
     fl = [feats.new_empty((N,), dtype=torch.float) for _ in range(2)]
     tt = [feats.new_empty((N, num_time_mask) if tm else (0,), dtype=torch.long) for _ in range(2)]
     ff = [feats.new_empty((N, num_freq_mask) if fm else (0,), dtype=torch.long) for _ in range(2)]
@@ -1079,7 +1092,7 @@ def _spec_forward_setup_context(ctx, inputs, output):
 def _spec_forward_backward(ctx, grads):
     grad_out = grads[0]  # (a List[Tensor] output: one list of gradients; the parameters carry none)
     w_0, w, t_0, t, f_0, f = ctx.params
-    ln = ctx.lengths if ctx.lengths is not None else torch.full((w_0.shape[0],), ctx.T, dtype=torch.long, device=w_0.device)
+    ln = ctx.lengths if ctx.lengths is not None else _full_lengths(w_0.shape[0], ctx.T, w_0.device)
     tgrid = torch.ops.pydrobert_amd.warp_1d_grid(w_0, w, ln, ctx.T, ctx.order)
     g = torch.ops.pydrobert_amd.spec_augment_apply_backward(
         grad_out, tgrid, None, t_0 if t_0.numel() else None, t if t.numel() else None,
@@ -1150,14 +1163,13 @@ def _spec_augment_apply(
         return torch.ops.pydrobert_amd.spec_augment_apply_warp(
             feats, w_0.to(device), w.to(device), lens_dev, interpolation_order, t0_, t_, f0_, f_, check
         )
-    lengths_ = lens_dev if lens_dev is not None else torch.full((N,), T, dtype=torch.long, device=device)
+    lengths_ = lens_dev if lens_dev is not None else _full_lengths(N, T, device)
     if _has(w_0, w):
         tgrid = warp_1d_grid(w_0.to(device), w.to(device), lengths_, T, interpolation_order)
     if _has(v_0, v):
         fgrid = warp_1d_grid(
-            v_0.to(device), v.to(device), torch.full((N,), F, dtype=torch.long, device=device), F,
-            interpolation_order,
-        )  # fmt: skip
+            v_0.to(device), v.to(device), _full_lengths(N, F, device), F, interpolation_order
+        )
     if tgrid is None and fgrid is None and t0_ is None and f0_ is None:
         _spec_augment_raise_unless(ok, T)
         return feats
@@ -1187,8 +1199,8 @@ def spec_augment(
         return feats
     if not feats.is_cuda:  # (host tensors are refused further on; the reference's order of errors)
         _spec_augment_raise_unless(_spec_augment_lengths_ok(feats, lengths), feats.size(1))
-    tm = max_time_mask != 0 and max_time_mask_proportion != 0.0 and num_time_mask != 0 and num_time_mask_proportion != 0.0
-    fm = max_freq_mask != 0 and num_freq_mask != 0
+    tm, fm = _masks_enabled(max_time_mask, max_time_mask_proportion, num_time_mask, num_time_mask_proportion,
+                            max_freq_mask, num_freq_mask)
     if feats.is_cuda and max_time_warp != 0.0 and max_freq_warp == 0.0 and feats.size(0) > 0:
         # the usual configuration: both halves behind one operator (csrc: the draw kernel, then the one-pass
         # application that solves the time warp's spline itself and judges the lengths)
@@ -1392,7 +1404,7 @@ class SpecAugment(torch.nn.Module):
 
     def forward(self, feats: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
         if lengths is None:
-            lengths = torch.full((feats.size(0),), feats.size(1), dtype=torch.long, device=feats.device)
+            lengths = _full_lengths(feats.size(0), feats.size(1), feats.device)
         if not self.training:
             return feats
         if not torch.jit.is_scripting():

@@ -180,7 +180,7 @@ def test_lm_interface_forward_idx_normalisation():
 
 
 def test_spec_augment_draw_parameters_refuses_cpu_tensors():
-    """The draw is one HIP kernel (csrc/img_warp.hip spec_augment_draw_kernel): like every operator of
+    """The draw is one HIP kernel (csrc/spec_augment.hip spec_augment_draw_kernel): like every operator of
     the package it refuses CPU tensors loudly instead of falling back (the ranges of the drawn
     parameters -- reference tests/test_img.py:226-281 -- are checked on the GPU, tests/test_img_gpu.py);
     a call that draws nothing needs no kernel and returns the reference's zero-size pairs."""

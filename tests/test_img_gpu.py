@@ -86,7 +86,7 @@ def test_spec_augment_apply_parameters(device, order, freq):
 def test_spec_augment_time_warp_in_one_launch(device, order):
     """``spec_augment_apply_parameters`` with a time warp and no frequency warp is ONE kernel (round 5):
     warp_1d_grid's three-knot spline is solved in closed form inside the pass over the features
-    (csrc/img_warp.hip warp_1d_spline).  Against the two-operator route through an explicit grid (the
+    (csrc/img_sample.hpp warp_1d_spline).  Against the two-operator route through an explicit grid (the
     Gauss-Jordan solve of ``warp_1d_grid``), against the float64 oracle on the valid frames, for lengths
     down to 1 / 2 / 3 frames, with and without masks, strided features (the grid route again), and the
     gradient of the fused operator against the grid route's."""
@@ -137,6 +137,42 @@ def test_spec_augment_time_warp_in_one_launch(device, order):
     # lengths out of range: the verdict comes after the launch, the error is the reference's
     with pytest.raises(RuntimeError, match="values of lengths"):
         F.spec_augment_apply_parameters(x, params, order, torch.full((N,), T + 1, device=device))
+
+
+def test_spec_augment_rows_two_tiles(device):
+    """The rows kernel's tile and column bookkeeping with more than one 256-row tile, at the smallest shape
+    that has it: T = 300 is two row tiles, the second partial; F = 12 is three float4 columns, no power
+    of two, so the reciprocal index split needs its fix-up.  One time mask (rows 250-260) straddles the
+    tile boundary, the frequency mask (columns 3-5) splits a float4, and the lengths sit on and next to
+    the boundary.  Against the float64 oracle on the valid frames, against the general kernel (the same
+    numbers as a stride-2 view: through the grid), and masked rows and columns exactly zero.
+    (Features uniform in [-0.5, 0.5]: neighbouring rows differ by at most 1, and the two spline solves,
+    both float64 rounded to a float32 grid, may differ by an ulp of the grid, 6e-8, which moves a tap by
+    150 * 6e-8 = 9e-6 rows -- inside the 2e-5 of the pair whatever the rows hold.)"""
+    rng = np.random.default_rng(77)
+    N, T, Fq, order = 3, 300, 12, 2
+    feats = rng.uniform(-0.5, 0.5, size=(N, T, Fq)).astype(np.float32)
+    lens = np.array([300, 257, 256])
+    w_0 = np.array([150.0, 120.5, 100.25], np.float32)
+    w = np.array([4.0, -2.5, 3.25], np.float32)
+    t_0 = np.array([[250, 10], [40, 250], [250, 255]]); t = np.array([[11, 5], [3, 11], [11, 1]])
+    f_0 = np.array([[3], [3], [3]]); f = np.array([[3], [3], [3]])
+    e = torch.empty(0)
+    params = (_t(w_0, device), _t(w, device), e, e, _t(t_0, device), _t(t, device), _t(f_0, device), _t(f, device))
+    ln = _t(lens, device)
+    act = F.spec_augment_apply_parameters(_t(feats, device), params, order, ln).cpu().numpy()
+    exp = oracle.spec_augment_apply_parameters(feats, (w_0, w, None, None, t_0, t, f_0, f), order, lens)
+    valid = np.arange(T)[None, :, None] < lens[:, None, None]
+    assert np.abs(np.where(valid, act - exp, 0)).max() < ATOL
+    wide = torch.zeros(N, T, 2 * Fq, device=device)
+    wide[:, :, ::2] = _t(feats, device)
+    gen = F.spec_augment_apply_parameters(wide[:, :, ::2], params, order, ln).cpu().numpy()
+    assert np.abs(np.where(valid, act - gen, 0)).max() < 2e-5
+    for n in range(N):
+        for m in range(2):
+            assert (act[n, t_0[n, m] : t_0[n, m] + t[n, m]] == 0).all()
+        assert (act[n, :, 3:6] == 0).all()
+        assert (act[n, :5, :3] != 0).all() and (act[n, 262:, 6:] != 0).all()
 
 
 def test_spec_augment_forward_behind_one_operator(device):
@@ -451,21 +487,31 @@ def test_spec_augment_backward_matches_grid_sample(device):
         assert torch.allclose(exp, act, atol=1e-4), (exp - act).abs().max().item()
 
 
-@pytest.mark.parametrize("monotone", [True, False])
-def test_spec_augment_rows_backward_any_grid(device, monotone):
+@pytest.mark.parametrize(
+    "monotone,T,Fq", [(True, 700, 8), (False, 700, 8), (True, 300, 12), (False, 300, 12)],
+    ids=["True", "False", "True-300x12", "False-300x12"])
+def test_spec_augment_rows_backward_any_grid(device, monotone, T, Fq):
     """The gather-form adjoint (time grid + masks, F % 4 == 0) for a non-decreasing grid and for
     an arbitrary one (where its row ranges degrade to full scans), both against autograd
-    through grid_sample; tiles: T > 256 rows."""
+    through grid_sample; tiles: T > 256 rows.  300 x 12: two tiles, the second partial, three float4
+    columns (the index split's fix-up), a time mask across the tile boundary, a frequency mask that
+    splits a float4."""
     torch.manual_seed(21 + monotone)
-    N, T, Fq = 3, 700, 8
+    N = 3
     feats = torch.randn(N, T, Fq, device=device)
     tgrid = torch.rand(N, T, device=device) * 2.4 - 1.2  # some samples clip at both borders
     if monotone:
         tgrid = tgrid.sort(1).values
-    t_0 = torch.tensor([[5, 300], [0, 650], [100, 100]], device=device)
-    t = torch.tensor([[10, 40], [3, 50], [0, 7]], device=device)
-    f_0 = torch.tensor([[1], [6], [0]], device=device)
-    f = torch.tensor([[2], [2], [0]], device=device)
+    if T == 700:
+        t_0 = torch.tensor([[5, 300], [0, 650], [100, 100]], device=device)
+        t = torch.tensor([[10, 40], [3, 50], [0, 7]], device=device)
+        f_0 = torch.tensor([[1], [6], [0]], device=device)
+        f = torch.tensor([[2], [2], [0]], device=device)
+    else:
+        t_0 = torch.tensor([[5, 250], [0, 255], [100, 100]], device=device)
+        t = torch.tensor([[10, 11], [3, 40], [0, 7]], device=device)
+        f_0 = torch.tensor([[3], [10], [0]], device=device)
+        f = torch.tensor([[3], [2], [0]], device=device)
     x = feats.clone().requires_grad_(True)
     y = torch.ops.pydrobert_amd.spec_augment_apply(x, tgrid, None, t_0, t, f_0, f)
     g = torch.randn_like(y)

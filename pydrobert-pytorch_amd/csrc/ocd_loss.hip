@@ -7,7 +7,10 @@
 //     loss[h, n] = 1/|S| * sum_{t in S} w_t * (logsumexp(logits[h, n, :]) - logits[h, n, t])
 // reading the logits row once.  Backward: d loss / d logits[v] =
 //     g * (Wsum / |S| * softmax[v] - [v in S] * w_v / |S|),   Wsum = sum_{t in S} w_t,
-// with set membership kept as a V-bit map in LDS.  Both passes are HBM-bound on the logits.
+// with set membership kept as a V-bit map in LDS for rows that fit the registers (V <= 1024).
+// Longer rows keep no map, so no vocabulary size is too large for the LDS: every element is written
+// with its softmax term, and once those stores are complete the elements of the targets are written
+// again with both terms.  Both passes are HBM-bound on the logits.
 #include "row_reduce.hpp"
 
 namespace pdt {
@@ -81,7 +84,7 @@ __global__ void __launch_bounds__(256) ocd_loss_kernel(const OcdArgs a) {
     wave_sync();
   }
   unsigned *member = reinterpret_cast<unsigned *>(smem + (size_t)4 * NR * PDT_WAVE * 4) + (size_t)wave * ((V + 31) / 32);
-  if (BACKWARD) {
+  if (BACKWARD && staged) {
     for (int i = lane; i < (V + 31) / 32; i += PDT_WAVE) member[i] = 0u;
     wave_sync();
   }
@@ -98,7 +101,7 @@ __global__ void __launch_bounds__(256) ocd_loss_kernel(const OcdArgs a) {
     acc += w * (lse - (staged ? xl[tok] : x[tok * a.lg_sv]));
     wsum += w;
     ++cnt;
-    if (BACKWARD) atomicOr(&member[tok >> 5], 1u << (tok & 31));
+    if (BACKWARD && staged) atomicOr(&member[tok >> 5], 1u << (tok & 31));
   });
   acc = wave_sum_f(acc);
   wsum = wave_sum_f(wsum);
@@ -115,17 +118,24 @@ __global__ void __launch_bounds__(256) ocd_loss_kernel(const OcdArgs a) {
   wave_sync();
   const float g = a.grad_loss[row] / denom;
   float *go = a.grad_logits + row * (int64_t)V;
-  auto grad_of = [&](const int v, const float xv) {
+  auto grad_of = [&](const int64_t v, const float xv, const bool in_set) {
     float gv = g * wsum * expf(xv - lse);
-    if ((member[v >> 5] >> (v & 31)) & 1u) gv -= g * (a.weight ? a.weight[v] : 1.0f);
+    if (in_set) gv -= g * (a.weight ? a.weight[v] : 1.0f);
     go[v] = gv;
   };
-  if (V <= NR * PDT_WAVE) {
+  if (staged) {
 #pragma unroll
-    for (int i = 0; i < NR; ++i)
-      if (i * PDT_WAVE < V && lane + i * PDT_WAVE < V) grad_of(lane + i * PDT_WAVE, r[i]);
+    for (int i = 0; i < NR; ++i) {
+      const int v = lane + i * PDT_WAVE;
+      if (i * PDT_WAVE < V && v < V) grad_of(v, r[i], (member[v >> 5] >> (v & 31)) & 1u);
+    }
   } else {
-    for (int v = lane; v < V; v += PDT_WAVE) grad_of(v, x[(int64_t)v * a.lg_sv]);
+    for (int v = lane; v < V; v += PDT_WAVE) grad_of(v, x[(int64_t)v * a.lg_sv], false);
+    __threadfence();  // the targets' elements are stored a second time, by other lanes: in this order
+    for_each_target(a, my_word, row, n, [&](int64_t tok) {
+      if (tok == a.ignore_index || tok < 0 || tok >= V) return;
+      grad_of(tok, x[tok * a.lg_sv], true);
+    });
   }
 }
 
@@ -137,9 +147,10 @@ static int ocd_launch(pdt::OcdArgs &a, bool backward, void *stream) {
   using namespace pdt;
   const int64_t rows = (int64_t)a.H * a.N;
   const bool small = a.V <= 8 * PDT_WAVE;
-  // staged rows of the four waves (64 NR floats each), then the membership maps of the backward pass
-  const size_t smem = (size_t)4 * (small ? 8 : 16) * PDT_WAVE * 4 + (backward ? (size_t)4 * ((a.V + 31) / 32) * 4 : 0);
-  if (smem > 64 * 1024) return PDT_E_TOO_LONG;
+  // staged rows of the four waves (64 NR floats each), then the membership maps of the backward pass;
+  // rows beyond the registers (V > 1024) use neither: at most 16.5 KiB, whatever V is
+  const bool staged = a.V <= 16 * PDT_WAVE;
+  const size_t smem = !staged ? 0 : (size_t)4 * (small ? 8 : 16) * PDT_WAVE * 4 + (backward ? (size_t)4 * ((a.V + 31) / 32) * 4 : 0);
   const unsigned grid = (unsigned)((rows + 3) / 4);
   auto kern = backward ? (small ? ocd_loss_kernel<true, 8> : ocd_loss_kernel<true, 16>)
                        : (small ? ocd_loss_kernel<false, 8> : ocd_loss_kernel<false, 16>);
@@ -154,6 +165,7 @@ int pdt_ocd_loss_forward(const float *logits, int64_t H, int64_t N, int64_t V, i
                          void *stream) {
   using namespace pdt;
   if (H < 0 || N < 0 || V < 1 || R < 0) return PDT_E_ARG;
+  if (V >= (1ll << 31)) return PDT_E_TOO_LONG;  // V is an int in the kernel, forward and backward alike
   if (H == 0 || N == 0) return PDT_OK;
   if (!logits || !bitmask || !class_tokens || !loss || !count) return PDT_E_ARG;
   if (H * N >= (1ll << 31) * 4) return PDT_E_TOO_LONG;
@@ -172,6 +184,7 @@ int pdt_ocd_loss_backward(const float *logits, int64_t H, int64_t N, int64_t V, 
                           void *stream) {
   using namespace pdt;
   if (H < 0 || N < 0 || V < 1 || R < 0) return PDT_E_ARG;
+  if (V >= (1ll << 31)) return PDT_E_TOO_LONG;  // V is an int in the kernel, forward and backward alike
   if (H == 0 || N == 0) return PDT_OK;
   if (!logits || !bitmask || !class_tokens || !grad_loss || !grad_logits) return PDT_E_ARG;
   if (H * N >= (1ll << 31) * 4) return PDT_E_TOO_LONG;

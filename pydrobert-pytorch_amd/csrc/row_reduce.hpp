@@ -9,7 +9,8 @@ namespace pdt {
 // kernels at eight waves per SIMD for the common vocabularies, 16 serves rows up to 1024.
 // One row x[0..V) (element stride sv) through a wave.  Returns the wave-wide maximum and, if asked,
 // the packed (value, lowest index) arg-max key and sum_v exp(x[v] - max).  Rows beyond 64 * NR
-// elements are streamed twice, eight loads in flight.
+// elements are streamed twice, eight loads in flight.  The arg-max compares values, not bit
+// patterns: -0 + 0 = +0 puts both zeros on one key, so that -0 and +0 tie and the lower index wins.
 struct RowStats {
   float mx, sum;
   u64 best;
@@ -39,7 +40,7 @@ __device__ __forceinline__ RowStats row_stats(const float *x, const int64_t sv, 
       if (i * PDT_WAVE < V) {
         mx = fmaxf(mx, r[i]);
         if (WANT_ARG && lane + i * PDT_WAVE < V) {
-          const u64 k = pack_key(fkey(r[i]), (unsigned)(lane + i * PDT_WAVE));
+          const u64 k = pack_key(fkey(r[i] + 0.0f), (unsigned)(lane + i * PDT_WAVE));
           best = k > best ? k : best;
         }
       }
@@ -53,7 +54,7 @@ __device__ __forceinline__ RowStats row_stats(const float *x, const int64_t sv, 
       for (int i = 0; i < 8; ++i) {
         mx = fmaxf(mx, t[i]);
         if (WANT_ARG && v0 + i * PDT_WAVE + lane < V) {
-          const u64 k = pack_key(fkey(t[i]), (unsigned)(v0 + i * PDT_WAVE + lane));
+          const u64 k = pack_key(fkey(t[i] + 0.0f), (unsigned)(v0 + i * PDT_WAVE + lane));
           best = k > best ? k : best;
         }
       }

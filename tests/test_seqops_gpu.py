@@ -170,3 +170,122 @@ def test_ctc_greedy_search_max_gradient(device, is_probs, batch_first):
     assert mx.requires_grad
     (mx * w.to(device)).sum().backward()
     assert torch.allclose(b.grad.cpu(), a.grad, rtol=1e-4, atol=1e-6)
+
+
+TIE_PAIRS = ((1, 129), (63, 64), (511, 512), (5, 2499))  # across lanes, register chunks, streamed blocks
+
+
+@pytest.mark.parametrize("is_probs", [False, True])
+@pytest.mark.parametrize("V", [130, 2500])
+def test_ctc_greedy_search_ties(device, V, is_probs):
+    """Equal maxima in two classes of a frame: the lower index wins (numpy's arg-max), wherever the two sit
+    -- in different lanes, register chunks or 512-element streamed blocks.  In the log domain one frame
+    more, whose maxima are -0.0 (class 0) and +0.0 (class 1): equal values, whatever their bit patterns."""
+    rng = np.random.default_rng(V)
+    pairs = [p for p in TIE_PAIRS if p[1] < V]
+    frames = []
+    for lo, hi in pairs:
+        x = rng.normal(size=V).astype(np.float32)
+        if is_probs:
+            x = (np.exp(x) / np.exp(x).sum()).astype(np.float32)
+        x[lo] = x[hi] = x.max() * np.float32(1.5) if is_probs else x.max() + np.float32(1)
+        frames.append(x)
+    want = [lo for lo, _ in pairs]
+    if not is_probs:
+        x = -1 - np.abs(rng.normal(size=V)).astype(np.float32)
+        x[0], x[1] = -0.0, 0.0
+        assert np.signbit(x[0]) and not np.signbit(x[1])
+        frames.append(x)
+        want.append(0)
+    lg = np.stack([np.stack(frames), np.stack(frames[::-1])], 1)  # (T, 2, V): the frames, and in reverse
+    blank = V - 2  # never a maximum, and no two neighbouring frames share theirs: nothing is collapsed
+    e_max, e_paths, e_lens = oracle.ctc_greedy_search(lg, None, blank, False, is_probs)
+    assert e_paths[:, 0].tolist() == want and e_paths[:, 1].tolist() == want[::-1]
+    a_max, a_paths, a_lens = F.ctc_greedy_search(T(lg, device), None, blank, False, is_probs)
+    assert np.array_equal(a_paths.cpu().numpy(), e_paths) and np.array_equal(a_lens.cpu().numpy(), e_lens)
+    assert np.allclose(a_max.cpu().numpy(), e_max, rtol=2e-5, atol=1e-3)
+
+
+@pytest.mark.parametrize("Tn", [8192, 8193, 20480])
+def test_ctc_greedy_search_long_inputs(device, Tn):
+    """The per-frame arg-max / value arrays in LDS: 64 KiB at 8192 frames (the last size without the
+    opt-in), one frame more, and the 160 KiB ceiling at 20480."""
+    rng = np.random.default_rng(Tn)
+    N, V = 2, 3
+    lg = rng.normal(size=(Tn, N, V)).astype(np.float32)
+    lens = np.array([Tn, Tn // 3])
+    e_max, e_paths, e_lens = oracle.ctc_greedy_search(lg, lens, 1, False, False)
+    a_max, a_paths, a_lens = F.ctc_greedy_search(T(lg, device), T(lens, device), 1)
+    assert np.array_equal(a_lens.cpu().numpy(), e_lens) and np.array_equal(a_paths.cpu().numpy(), e_paths)
+    assert np.allclose(a_max.cpu().numpy(), e_max, rtol=2e-5, atol=1e-3)
+
+
+def strided_view(base, layout):
+    """``base[..., ::2]`` (class stride 2) of a (T, N, 2V) tensor, or a (V, T, N) tensor seen as (T, N, V)
+    (the class axis outermost in memory)."""
+    return base[..., ::2] if layout == "every_other" else (base.permute(1, 2, 0) if hasattr(base, "permute") else base.transpose(1, 2, 0))
+
+
+@pytest.mark.parametrize("layout", ["every_other", "vocab_outermost"])
+@pytest.mark.parametrize("V", [65, 1100])
+def test_ctc_greedy_search_strided_logits(device, V, layout):
+    rng = np.random.default_rng(V)
+    Tn, N = 20, 3
+    base = rng.normal(size=(Tn, N, 2 * V) if layout == "every_other" else (V, Tn, N)).astype(np.float32) * 3
+    lens = np.array([Tn, 7, 0])
+    x = strided_view(T(base, device), layout)
+    assert x.shape == (Tn, N, V) and x.stride(2) == (2 if layout == "every_other" else Tn * N)
+    for is_probs in (False, True):
+        e_max, e_paths, e_lens = oracle.ctc_greedy_search(strided_view(base, layout), lens, V - 1, False, is_probs)
+        a_max, a_paths, a_lens = F.ctc_greedy_search(x, T(lens, device), V - 1, False, is_probs)
+        assert np.array_equal(a_lens.cpu().numpy(), e_lens) and np.array_equal(a_paths.cpu().numpy(), e_paths)
+        assert np.allclose(a_max.cpu().numpy(), e_max, rtol=2e-5, atol=1e-3)
+
+
+@pytest.mark.parametrize("V", [70, 1100])
+def test_ctc_greedy_search_frames_beyond_the_length(device, V):
+    """Frames beyond ``in_lens`` that hold nothing but -inf leave ``max_`` finite (they contribute 0), and
+    the tail of ``paths`` reports their arg-max (class 0) as the reference does."""
+    rng = np.random.default_rng(V)
+    Tn, N = 12, 3
+    lg = rng.normal(size=(Tn, N, V)).astype(np.float32) * 3
+    lens = np.array([Tn, 5, 0])
+    for n in range(N):
+        lg[lens[n]:, n] = -np.inf
+    with np.errstate(all="ignore"):
+        e_max, e_paths, e_lens = oracle.ctc_greedy_search(lg, lens, V - 1, False, False)
+    assert np.isfinite(e_max).all() and not e_paths[5:, 1].any() and not e_paths[:, 2].any()
+    a_max, a_paths, a_lens = F.ctc_greedy_search(T(lg, device), T(lens, device), V - 1)
+    assert torch.isfinite(a_max).all()
+    assert np.array_equal(a_lens.cpu().numpy(), e_lens) and np.array_equal(a_paths.cpu().numpy(), e_paths)
+    assert np.allclose(a_max.cpu().numpy(), e_max, rtol=2e-5, atol=1e-3)
+
+
+@pytest.mark.parametrize("V", [65, 1100])
+def test_sequence_log_probs_non_contiguous(device, V):
+    """``base[..., ::2]``: the forward result, and the gradient that reaches ``base``, against float64."""
+    rng = np.random.default_rng(V)
+    S, N = 9, 3
+    base = rng.normal(size=(S, N, 2 * V)).astype(np.float32) * 3
+    hyp = rng.integers(0, V, (S, N))
+    eos = V - 1
+    hyp[hyp == eos] = 0
+    hyp[4, 1] = eos
+    hyp[2, 2] = -1
+    b = T(base, device).requires_grad_(True)
+    x = b[..., ::2]
+    assert not x.is_contiguous()
+    act = F.sequence_log_probs(x, T(hyp, device), 0, eos)
+    exp = oracle.sequence_log_probs(base[..., ::2], hyp, 0, eos)
+    assert np.allclose(act.detach().cpu().numpy(), exp, rtol=2e-5, atol=1e-4)
+    gw = torch.randn(N, dtype=torch.double)
+    (act * gw.float().to(device)).sum().backward()
+    b64 = torch.from_numpy(base).double().requires_grad_(True)
+    h = torch.from_numpy(hyp)
+    first = torch.where((h == eos).any(0), (h == eos).long().argmax(0), torch.tensor(S)) + 1
+    mask = (h < 0) | (torch.arange(S).unsqueeze(1) >= first.unsqueeze(0))
+    ref = b64[..., ::2].log_softmax(-1).gather(-1, h.masked_fill(mask, 0).unsqueeze(-1)).squeeze(-1).masked_fill(mask, 0.0).sum(0)
+    (ref * gw).sum().backward()
+    assert torch.allclose(torch.from_numpy(ref.detach().numpy()), act.detach().cpu().double(), rtol=2e-5, atol=1e-4)
+    assert torch.allclose(b.grad.cpu().double(), b64.grad, rtol=1e-4, atol=1e-5)
+    assert not b.grad[..., 1::2].any()

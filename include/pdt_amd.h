@@ -658,16 +658,16 @@ int pdt_fusion_ext(const float *lm_log_probs, int64_t N, int64_t Kp, int64_t V, 
  *   ... + pad[1,n]                             right padding;  the rest: *fill
  * mode 0 constant (*fill), 1 reflect (x[n, pad0 - t], x[n, lens - 2 - j]; the caller checks
  * pad < lens), 2 replicate (x[n, 0], x[n, lens - 1]; the caller checks lens >= 1).
- * pdt_pad_variable_backward: float32 adjoint with respect to x, written as a gather
- * (deterministic); grad_out (N, Tp, F), grad_x (N, T, F).
+ * pdt_pad_variable_backward: the adjoint with respect to x, written as a gather (deterministic),
+ * dtype 0 float32 / 1 float64; grad_out (N, Tp, F), grad_x (N, T, F) of that type.
  * ------------------------------------------------------------------------------------- */
 int pdt_pad_variable(const void *x, int64_t N, int64_t T, int64_t F, int64_t elem_bytes,
                      const int64_t *lens, const int64_t *pad, int mode, const void *fill,
                      int64_t Tp, void *out, void *stream);
 
-int pdt_pad_variable_backward(const float *grad_out, int64_t N, int64_t T, int64_t F,
+int pdt_pad_variable_backward(const void *grad_out, int dtype, int64_t N, int64_t T, int64_t F,
                               const int64_t *lens, const int64_t *pad, int mode, int64_t Tp,
-                              float *grad_x, void *stream);
+                              void *grad_x, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Feature deltas (reference _feats.py:216-286).  x is indexed (A, B, T, C, D) with element

@@ -219,10 +219,14 @@ __global__ void __launch_bounds__(kFeatThreads) feat_deltas_backward_kernel(cons
   const int64_t T_ = a.T, P = a.P;
   CT acc = delta_adjoint_at<CT>(a, g, taps, s);
   if (a.mode == DPAD_REPLICATE) {
+    // the P copies of an end sample are summed on their own: each is far smaller than the sample's own
+    // term, and added to it one by one a wide halo's copies round away (1e-4 of the gradient at P = 8191)
+    CT edge = CT(0);
     if (s == 0)
-      for (int64_t j = -P; j < 0; ++j) acc += delta_adjoint_at<CT>(a, g, taps, j);
+      for (int64_t j = -P; j < 0; ++j) edge += delta_adjoint_at<CT>(a, g, taps, j);
     if (s == T_ - 1)
-      for (int64_t j = T_; j < T_ + P; ++j) acc += delta_adjoint_at<CT>(a, g, taps, j);
+      for (int64_t j = T_; j < T_ + P; ++j) edge += delta_adjoint_at<CT>(a, g, taps, j);
+    acc += edge;
   } else if (a.mode == DPAD_REFLECT) {
     if (s >= 1 && s <= P) acc += delta_adjoint_at<CT>(a, g, taps, -s);
     if (s <= T_ - 2 && s >= T_ - 1 - P) acc += delta_adjoint_at<CT>(a, g, taps, 2 * (T_ - 1) - s);

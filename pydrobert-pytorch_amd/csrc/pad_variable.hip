@@ -7,8 +7,8 @@
 // the fill value (inputs up to 2^32 elements per call).  Elements are moved as opaque 1/2/4/8-byte words, so every dtype is served by
 // four instantiations.  HBM-bound: one read of the valid input, one write of the output.
 //
-// Backward (float32) is the adjoint written as a gather, so it is deterministic: an input
-// element collects the gradient of its own copy plus those of its reflections / replications.
+// Backward (float32 or float64) is the adjoint written as a gather, so it is deterministic: an
+// input element collects the gradient of its own copy plus those of its reflections / replications.
 #include "pdt_common.hpp"
 
 namespace pdt {
@@ -65,9 +65,10 @@ __global__ void __launch_bounds__(256) pad_variable_kernel(const PadArgs a, unsi
 }
 
 // grad_x[n, s, :] = sum of grad_out over the output positions that read x[n, s, :]
+template <typename G>
 __global__ void __launch_bounds__(256)
-pad_variable_backward_kernel(const PadArgs a, const float *__restrict__ grad_out,
-                             float *__restrict__ grad_x, unsigned total) {
+pad_variable_backward_kernel(const PadArgs a, const G *__restrict__ grad_out,
+                             G *__restrict__ grad_x, unsigned total) {
   const unsigned F = (unsigned)a.F, T = (unsigned)a.T;
 #pragma unroll
   for (int i = 0; i < kPerThread; ++i) {
@@ -77,8 +78,8 @@ pad_variable_backward_kernel(const PadArgs a, const float *__restrict__ grad_out
     const unsigned n = row / T;
     const int64_t s = row - n * T;
     const int64_t len = a.lens[n], left = a.pad[n], right = a.pad[a.N + n];
-    const float *go = grad_out + (int64_t)n * a.Tp * F + f;
-    float acc = 0.0f;
+    const G *go = grad_out + (int64_t)n * a.Tp * F + f;
+    G acc = G(0);
     if (s < len) {
       acc = go[(left + s) * F];
       if (a.mode == PADMODE_REFLECT) {
@@ -124,11 +125,11 @@ int pdt_pad_variable(const void *x, int64_t N, int64_t T, int64_t F, int64_t ele
   return (int)hipGetLastError();
 }
 
-int pdt_pad_variable_backward(const float *grad_out, int64_t N, int64_t T, int64_t F,
+int pdt_pad_variable_backward(const void *grad_out, int dtype, int64_t N, int64_t T, int64_t F,
                               const int64_t *lens, const int64_t *pad, int mode, int64_t Tp,
-                              float *grad_x, void *stream) {
+                              void *grad_x, void *stream) {
   using namespace pdt;
-  if (N < 0 || T < 0 || F < 0 || Tp < 0 || mode < 0 || mode > 2) return PDT_E_ARG;
+  if (N < 0 || T < 0 || F < 0 || Tp < 0 || mode < 0 || mode > 2 || dtype < 0 || dtype > 1) return PDT_E_ARG;
   if (N == 0 || T == 0 || F == 0) return PDT_OK;
   if (!grad_out || !lens || !pad || !grad_x) return PDT_E_ARG;
   if (N * T * F >= (1ll << 32) - 1024 * kPerThread) return PDT_E_TOO_LONG;
@@ -136,8 +137,14 @@ int pdt_pad_variable_backward(const float *grad_out, int64_t N, int64_t T, int64
   a.lens = lens; a.pad = pad; a.N = (int)N; a.T = (int)T; a.F = (int)F; a.Tp = (int)Tp;
   a.mode = mode;
   const unsigned total = (unsigned)(N * T * F);
-  hipLaunchKernelGGL(pad_variable_backward_kernel, dim3((total + 256 * kPerThread - 1) / (256 * kPerThread)),
-                     dim3(256), 0, (hipStream_t)stream, a, grad_out, grad_x, total);
+  const dim3 grid((total + 256 * kPerThread - 1) / (256 * kPerThread));
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == 0)
+    hipLaunchKernelGGL(pad_variable_backward_kernel<float>, grid, dim3(256), 0, s, a, (const float *)grad_out,
+                       (float *)grad_x, total);
+  else
+    hipLaunchKernelGGL(pad_variable_backward_kernel<double>, grid, dim3(256), 0, s, a, (const double *)grad_out,
+                       (double *)grad_x, total);
   return (int)hipGetLastError();
 }
 

@@ -17,9 +17,10 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 
 # what pdt_amd_abi_version() must report: the table below is this version's.  A change of the table bumps it
 # on both sides.  The one exception so far: the return and combinatorics entry points were added at 12,
-# because tests/test_random_walk_cpu.py pins that number; a library built before them is still refused by
-# lib(), with its missing-entry-point message in place of the version one.
-ABI_VERSION = 12
+# because tests/test_random_walk_cpu.py pinned that number; a library built before them is still refused by
+# lib(), with its missing-entry-point message in place of the version one.  13: pdt_pad_variable_backward takes
+# the gradient's dtype (a library of version 12 would read the arguments one place off).
+ABI_VERSION = 13
 
 PDT_OK = 0
 PDT_E_ARG = -1
@@ -184,7 +185,7 @@ SIGNATURES = {
     ),
     "pdt_fusion_ext": (_INT, [_P, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _F, _INT, _P, _P]),
     "pdt_pad_variable": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P, _INT, _P, _I64, _P, _P]),
-    "pdt_pad_variable_backward": (_INT, [_P, _I64, _I64, _I64, _P, _P, _INT, _I64, _P, _P]),
+    "pdt_pad_variable_backward": (_INT, [_P, _INT, _I64, _I64, _I64, _P, _P, _INT, _I64, _P, _P]),
     "pdt_feat_deltas": (
         _INT, [_P, _INT, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _INT, _P, _INT, _P, _P],
     ),

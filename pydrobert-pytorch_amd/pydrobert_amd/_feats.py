@@ -53,22 +53,33 @@ def _prod(sizes) -> int:
 # deltas
 
 
-def _feat_delta_filters(order: int, width: int) -> torch.Tensor:
-    """The (order + 1, 1 + 2P) composite taps in float32, P = width * order.  Row 0 picks the centre
-    sample; row u is row u - 1 cross-correlated with the slope kernel k[i] = (width - i) / sum_j j^2,
-    i = 0 .. 2 * width, the row zero-padded by ``width`` on each side first."""
+def _check_order_width(order: int, width: int) -> None:
     if order < 0 or width < 1:
         raise RuntimeError(
             "feature deltas need order >= 0 and width >= 1 (order={}, width={})".format(order, width)
         )
+
+
+def _feat_delta_filters(order: int, width: int) -> torch.Tensor:
+    """The (order + 1, 1 + 2P) composite taps in float32, P = width * order.  Row 0 picks the centre
+    sample; row u is row u - 1 cross-correlated with the slope kernel k[i] = (width - i) / sum_j j^2,
+    i = 0 .. 2 * width, the row zero-padded by ``width`` on each side first.
+
+    The correlation is spelt out, one slope tap after the other with each partial sum rounded to float32
+    (the product of two float32 numbers is exact in float64): conv1d rounds differently from one CPU's
+    vector units to another's, and these are the reference's filters bit for bit on all of them."""
+    _check_order_width(order, width)
     K = 1 + 2 * width * order
     slope = torch.linspace(width, -width, 2 * width + 1, dtype=torch.float32)
-    slope = (slope / slope.pow(2).sum()).view(1, 1, -1)
+    slope = (slope / slope.pow(2).sum()).double()
     taps = torch.zeros((order + 1, K), dtype=torch.float32)
     taps[0, K // 2] = 1.0
     for u in range(1, order + 1):
-        padded = torch.nn.functional.pad(taps[u - 1], (width, width)).view(1, 1, -1)
-        taps[u] = torch.nn.functional.conv1d(padded, slope).view(-1)
+        padded = torch.nn.functional.pad(taps[u - 1], (width, width)).double()
+        acc = torch.zeros(K, dtype=torch.float64)
+        for i in range(2 * width + 1):
+            acc = (acc + slope[i] * padded[i:i + K]).float().double()
+        taps[u] = acc.float()
     return taps
 
 
@@ -118,7 +129,7 @@ def _delta_out_shape(shape: List[int], k: int, U: int, concatenate: bool) -> Lis
 
 def _delta_checks(shape, filters, dim, time_dim, concatenate, order, width, pad_mode, value=0.0):
     if filters is None:
-        _feat_delta_filters(order, width)  # (the reference builds them first: its errors come first)
+        _check_order_width(order, width)  # (the reference builds them first: its errors come first)
     else:
         assert tuple(filters.shape) == (order + 1, 1 + (2 * width) * order)
     t, k = _delta_geometry(list(shape), dim, time_dim, concatenate)

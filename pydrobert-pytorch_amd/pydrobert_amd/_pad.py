@@ -80,16 +80,17 @@ def _pad_variable_backward_op(
     grad_out: torch.Tensor, lens: torch.Tensor, pad: torch.Tensor, mode: str, T: int
 ) -> torch.Tensor:
     device = _cabi.require_hip(grad_out, lens, pad)
-    g = grad_out.detach().float().contiguous()
+    ct = torch.float64 if grad_out.dtype == torch.float64 else torch.float32
+    g = grad_out.detach().to(ct).contiguous()
     N, Tp = g.shape[0], g.shape[1]
     F = 1
     for d in g.shape[2:]:
         F *= d
     ln, pd = lens.detach().long().contiguous(), pad.detach().long().contiguous()
     with torch.cuda.device(device):
-        grad = torch.empty((N, T) + tuple(g.shape[2:]), device=device, dtype=torch.float)
+        grad = torch.empty((N, T) + tuple(g.shape[2:]), device=device, dtype=ct)
         rc = _cabi.lib().pdt_pad_variable_backward(
-            _cabi.ptr(g) if g.numel() else None, N, T, F, _cabi.ptr(ln), _cabi.ptr(pd),
+            _cabi.ptr(g) if g.numel() else None, int(ct == torch.float64), N, T, F, _cabi.ptr(ln), _cabi.ptr(pd),
             _PAD_MODES[mode], Tp, _cabi.ptr(grad) if grad.numel() else None, _cabi.stream_ptr(device),
         )  # fmt: skip
     _cabi.check(rc, "pdt_pad_variable_backward")

@@ -87,7 +87,7 @@ def test_spec_augment_time_warp_in_one_launch(device, order):
     """``spec_augment_apply_parameters`` with a time warp and no frequency warp is ONE kernel (round 5):
     warp_1d_grid's three-knot spline is solved in closed form inside the pass over the features
     (csrc/img_sample.hpp warp_1d_spline).  Against the two-operator route through an explicit grid (the
-    Gauss-Jordan solve of ``warp_1d_grid``), against the float64 oracle on the valid frames, for lengths
+    elimination of ``warp_1d_grid``'s kernel), against the float64 oracle on the valid frames, for lengths
     down to 1 / 2 / 3 frames, with and without masks, strided features (the grid route again), and the
     gradient of the fused operator against the grid route's."""
     rng = np.random.default_rng(60 + order)
@@ -678,3 +678,308 @@ def test_float64_images_are_narrowed_out_loud(device):
         act2 = F.dense_image_warp(img.double(), flow.double())
     assert act.dtype == torch.double and torch.allclose(act.float(), exp, atol=1e-6) and torch.equal(act, act2)
     assert sum("float64" in str(x.message) for x in w) == 1
+
+
+# ---------------------------------------------------------------------------------------
+# every instance and launch form of the warp and spline kernels (references, tolerances and the
+# conditions of the shapes: tests/_img_ref.py, pinned without a GPU by tests/test_img_cpu.py)
+# ---------------------------------------------------------------------------------------
+import _img_ref as R  # noqa: E402
+
+
+def _sparse(case, device, indexing, padding, img=None):
+    s, d = case.points(indexing)
+    image = case.image if img is None else img
+    return F.sparse_image_warp(_t(image, device), _t(s, device), _t(d, device), indexing, case.order,
+                               pinned_boundary_points=case.pinned, dense_interpolation_mode=case.mode,
+                               dense_padding_mode=padding, include_flow=case.include_flow)  # fmt: skip
+
+
+def _check_sparse(case, device, padding, indexings=R.INDEXINGS):
+    """One sparse warp against ``oracle.grid_sample`` at the oracle's own grid: values within 1e-5 + pos_tol x
+    lipschitz(image, padding), pos_tol = 4 x the float32 error of the reference's own evaluation (floor 2e-5
+    px); the flow, where there is one, within pos_tol; nearest mode on the pixels whose position is further
+    than pos_tol from a rounding boundary (at most 1 % are not)."""
+    N, C, H, W = case.shape
+    ptol = case.ptol()
+    tol = R.value_tol(ptol, case.image, padding)
+    assert R.sensitive(tol, case.image)
+    for indexing in indexings:
+        exp = case.expected(indexing, padding)
+        out = _sparse(case, device, indexing, padding)
+        if case.include_flow:
+            flow = out[1].cpu().numpy()
+            ferr = np.abs(flow - case.grid(indexing)[1]).max()
+            print(case.name, padding, indexing, "flow err %.3g of %.3g px" % (ferr, ptol))
+            assert flow.shape == (N, H, W, 2) and ferr <= ptol, (case.name, indexing, ferr, ptol)
+            out = out[0]
+        act = out.cpu().numpy()
+        assert act.dtype == case.dtype and act.shape == exp.shape
+        err = np.abs(act.astype(np.float64) - exp)
+        if case.mode == "nearest":
+            ok = R.off_boundary(R.positions(case.grid(indexing)[0], H, W), H, W, padding, ptol)
+            assert 1.0 - ok.mean() <= R.MAX_BOUNDARY_SHARE
+            err = err * ok[:, None]
+        print(case.name, padding, indexing, "err %.3g of %.3g (pos_tol %.3g px)" % (err.max(), tol, ptol))
+        assert np.isfinite(act).all() and err.max() <= tol, (case.name, padding, indexing, err.max(), tol)
+
+
+@pytest.mark.parametrize("Mp", [7, 8, 4, 5])
+@pytest.mark.parametrize("padding", R.PADDINGS)
+@pytest.mark.parametrize("order", [1, 2, 3, 4])
+def test_sparse_warp_bands_every_instance(device, order, padding, Mp):
+    """``sparse_warp_bands_kernel<ORDER, PADDING, MC>``: float32, bilinear, no flow.  order 1-3 are the
+    compiled orders, 4 the run-time one (ORDER = 0); M' = 7 (3 points + 4 pinned corners) is MC = 7, M' = 8
+    (4 + 4) is MC = 8 -- the 24 instances -- and M' = 4, 5 (unpinned) are MC = 8 with zero-weight filler
+    centres.  2 x 2 x 37 x 29: ten bands of four rows, the last with ONE real row (the store guard, taps of
+    rows past H); 290 lanes, so a second workgroup with 34 of them, a partial wave; two images (the table's
+    per-image stride: 36 floats at MC = 7, 40 at MC = 8), two planes (the plane loop); no smaller shape has
+    all of these.  The control points push 12-32 % of the samples beyond each of the four sides, so the zeros
+    kernels' select and clamped tap addresses, the reflection fold and the border clamp all work on every
+    side.  Both indexings.  Measured pos_tol_sparse (float32 plain sum against float64, CPU): 1.0e-5 to
+    2.9e-4 px at M' = 7, 8 (largest at order 4), 1.1e-5 to 2.2e-5 px at M' = 4, 5; tolerances 4 x that."""
+    _check_sparse(R.SPARSE_CASES["bands-o%d-m%d" % (order, Mp)], device, padding)
+
+
+@pytest.mark.parametrize("padding", R.PADDINGS)
+def test_sparse_warp_bands_reflection_folds_twice(device, padding):
+    """Unpinned M' = 4 whose displacements are 2.5 image sizes: 46 % of the samples lie beyond each side, most
+    of them more than a whole image out, so ``reflect_coord``'s flip count reaches 2 and more (both
+    parities), and the zeros kernel converts positions far outside to tap indices.  Measured pos_tol_sparse
+    9.6e-5 px."""
+    _check_sparse(R.SPARSE_CASES["bands-fold"], device, padding)
+
+
+@pytest.mark.parametrize("padding", R.PADDINGS)
+@pytest.mark.parametrize("H", [5, 3])
+def test_sparse_warp_bands_edges(device, H, padding):
+    """Band edges at W = 7, unpinned M' = 4: H = 5 is two bands, the second with one real row; H = 3 a
+    single partial band (an image with fewer rows than a band).  The smallest heights with these; one
+    partial workgroup.  Measured pos_tol_sparse 3.7e-6 / 3.5e-6 px: the 2e-5 px floor applies."""
+    _check_sparse(R.SPARSE_CASES["edge-h%d" % H], device, padding)
+
+
+@pytest.mark.parametrize("Mp", [7, 8])
+@pytest.mark.parametrize("padding", R.PADDINGS)
+def test_sparse_warp_bands_no_real_pixel_for_an_outside_tap(device, padding, Mp):
+    """Column 0 and row 0 of the image are +inf (37 x 29, order 2, the shape of the instance test).  A
+    sample clamped onto the last column has x0 = W - 1: its right neighbour is one float further in memory,
+    column 0 of the next row -- an inf; the same for the last row and the next plane (row 0).  The border
+    and reflection kernels must step beyond the buffer there, the zeros kernel must drop the taps it loaded
+    from clamped addresses with a select: inf x 0 would be NaN.  An output pixel is finite and within
+    tolerance if its float64 taps, widened by pos_tol, exclude the inf pixels, and non-finite if a tap with
+    weight above pos_tol is one."""
+    case = R.SPARSE_CASES["bands-o2-m%d" % Mp]
+    N, C, H, W = case.shape
+    ptol = case.ptol()
+    img = case.image.copy()
+    img[:, :, 0, :] = np.inf
+    img[:, :, :, 0] = np.inf
+    tol = R.value_tol(ptol, case.image, padding)
+    pos = R.positions(case.grid("hw")[0], H, W)
+    lo, hi = R.tap_pixels(pos, H, W, padding, ptol)
+    clean = np.ones(pos.shape[:-1], bool)
+    for k in range(2):  # no pixel of index 0 among the taps that lie inside the image
+        clean &= ~((lo[..., k] <= 0) & (hi[..., k] >= 0))
+    p = R.pad_positions(pos, H, W, padding)
+    p0 = np.floor(p)
+    w1 = p - p0
+    must = np.zeros(pos.shape[:-1], bool)
+    size = np.array([W, H])
+    for dx in (0, 1):
+        for dy in (0, 1):
+            tx, ty = p0[..., 0] + dx, p0[..., 1] + dy
+            wgt = (w1[..., 0] if dx else 1 - w1[..., 0]) * (w1[..., 1] if dy else 1 - w1[..., 1])
+            inside = (tx >= 0) & (tx < size[0]) & (ty >= 0) & (ty < size[1])
+            must |= inside & ((tx == 0) | (ty == 0)) & (wgt > ptol)
+    assert clean.mean() > 0.2 and must.mean() > 0.02 and not (clean & must).any()
+    # clean, and clamped onto the last column / row: the neighbour in memory is an inf pixel
+    if padding == "zeros":  # (all taps left of / above the image: their clamped addresses are inf pixels)
+        assert (clean & (p[..., 0] < -1)).sum() > 10 and (clean & (p[..., 1] < -1)).sum() > 10
+    else:
+        assert (clean & (p[..., 0] == W - 1)).sum() > 10 and (clean & (p[..., 1] == H - 1)).sum() > 10
+    exp = case.expected("hw", padding)  # (clean pixels read no pixel of row / column 0: the finite image's)
+    act = _sparse(case, device, "hw", padding, img).cpu().numpy()
+    fin = np.isfinite(act)
+    cm, mm = np.broadcast_to(clean[:, None], act.shape), np.broadcast_to(must[:, None], act.shape)
+    assert fin[cm].all(), "%d clean pixels are not finite" % (~fin[cm]).sum()
+    assert np.abs(act[cm] - exp[cm]).max() <= tol
+    assert not fin[mm].any()
+
+
+@pytest.mark.parametrize("Mp", [7, 8])
+@pytest.mark.parametrize("padding", R.PADDINGS)
+def test_sparse_warp_bands_forward_against_general_adjoint(device, padding, Mp):
+    """The fast forward (sparse_warp_bands_kernel, no flow, M' = 7 / 8) tied to its adjoint, which is
+    image_warp_kernel<BACKWARD> on the sparse route (10 + lanes; 37 x 29): <op(x + d) - op(x), g> against
+    <d, op^T g> at the 1e-3 of test_sparse_image_warp_backward."""
+    case = R.SPARSE_CASES["bands-o2-m%d" % Mp]
+    s, d = (_t(a, device) for a in case.points("hw"))
+
+    def op(x):
+        return F.sparse_image_warp(x, s, d, pinned_boundary_points=case.pinned, dense_padding_mode=padding,
+                                   include_flow=False)  # fmt: skip
+
+    lhs, rhs, _ = _adjoint_gap(op, _t(case.image, device))
+    assert abs(lhs - rhs) <= 1e-3 * max(1.0, abs(lhs)), (lhs, rhs)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64], ids=["f32", "f64"])
+@pytest.mark.parametrize("padding", R.PADDINGS)
+@pytest.mark.parametrize("mode", R.MODES)
+def test_dense_image_warp_two_workgroups(device, mode, padding, dtype):
+    """``image_warp_kernel`` beyond one workgroup, dense route, forward and adjoint, float32 and float64:
+    2 x 2 x 50 x 45 is 2250 pixels, so blockIdx.x = 1 covers 202 and its last pass of 256 is partial -- the
+    smallest second workgroup that has both a full wave and a partial one.  Forward against the oracle
+    (float32: pos_tol = 8 * 2^-24 * 50 = 2.4e-5 px, values within 1e-5 + pos_tol x lipschitz; float64: the
+    suite's 1e-12); the adjoint against float64 autograd through torch's grid_sample on the CPU, within
+    1e-5 + (2 pos_tol + 2^-22) x the |g| mass that can reach a pixel (adjoint_mass; float64: 1e-12 x that),
+    and ``_adjoint_gap``.  Nearest mode leaves out the samples within pos_tol of a rounding boundary (at
+    most 1 %; about 0.01 % here).  Both indexings."""
+    img, flow = R.dense_case(dtype=dtype)
+    N, C, H, W = img.shape
+    f64 = dtype == np.float64
+    ptol = 1e-12 if f64 else R.pos_tol_dense(H, W)
+    tol = 1e-12 if f64 else R.value_tol(ptol, img, padding)
+    assert R.sensitive(tol, img)
+    g = np.random.default_rng(17).normal(size=img.shape).astype(dtype)
+    for indexing in R.INDEXINGS:
+        grid = R.dense_grid(flow, indexing, H, W, dtype)
+        pos = R.positions(grid, H, W)
+        ok = np.ones(pos.shape[:-1], bool)
+        if mode == "nearest":
+            ok = R.off_boundary(pos, H, W, padding, ptol)
+            assert 1.0 - ok.mean() <= R.MAX_BOUNDARY_SHARE
+        exp = oracle.grid_sample(img, grid, mode, padding)
+        x = _t(img, device).requires_grad_(True)
+        y = F.dense_image_warp(x, _t(flow, device), indexing, mode, padding)
+        act = y.detach().cpu().numpy()
+        assert act.dtype == dtype
+        err = (np.abs(act.astype(np.float64) - exp) * ok[:, None]).max()
+        print(mode, padding, indexing, "err %.3g of %.3g" % (err, tol))
+        assert err <= tol, (indexing, err, tol)
+        # adjoint: grad_out zero on the left-out samples
+        gm = g * ok[:, None]
+        (gx,) = torch.autograd.grad(y, x, _t(gm, device))
+        gexp = R.adjoint_reference(grid, gm, H, W, mode, padding)
+        mass = R.adjoint_mass(pos, gm, H, W, padding, ptol)[:, None]
+        gtol = 1e-12 * np.maximum(mass, 1.0) if f64 else 1e-5 + (2 * ptol + 2.0**-22) * mass
+        gerr = np.abs(gx.cpu().numpy().astype(np.float64) - gexp)
+        print(mode, padding, indexing, "adjoint err %.3g, largest tolerance %.3g" % (gerr.max(), gtol.max()))
+        assert gx.dtype == x.dtype and (gerr <= gtol).all(), (indexing, (gerr / gtol).max())
+        assert np.median(gtol) <= 0.1 * np.median(np.abs(gexp[gexp != 0]))  # a misplaced tap cannot pass
+    if mode == "nearest":  # (an exact adjoint pair away from the boundaries, which the random d does not move)
+        return
+    fl = _t(flow, device)
+    lhs, rhs, _ = _adjoint_gap(lambda t: F.dense_image_warp(t, fl, "hw", mode, padding), _t(img, device))
+    assert abs(lhs - rhs) <= (1e-9 if f64 else 1e-3) * max(1.0, abs(lhs)), (lhs, rhs)
+
+
+@pytest.mark.parametrize("padding", R.PADDINGS)
+@pytest.mark.parametrize("name", ["general-flow-m7", "general-m12", "general-nearest-m7", "general-o4-m9", "general-f64-m7"])
+def test_sparse_image_warp_general_route_two_workgroups(device, name, padding):
+    """``image_warp_kernel`` on the sparse route (knots and weights staged in LDS by each workgroup) at 2 x 2 x
+    50 x 45, where a second workgroup stages them again and covers 202 pixels: with the flow written out
+    (M' = 7; the second workgroup's flow is checked like the first's, within pos_tol), with more centres than
+    the fast kernel takes (M' = 12), in nearest mode (M' = 7), at order 4 (M' = 9: the run-time order of
+    the centre loop) and on a float64 image (M' = 7: the double instantiation), each under every padding.
+    Measured pos_tol_sparse: 1.6e-4 (flow), 4.8e-4 (M' = 12), 1.5e-4 (nearest, float64), 4.0e-4 px (order 4)."""
+    _check_sparse(R.SPARSE_CASES[name], device, padding, ("hw",) if padding != "border" else R.INDEXINGS)
+
+
+def test_dense_image_warp_eight_million_pixels(device):
+    """The H * W >= 2^23 branch of ``image_warp_kernel`` (an integer division in place of ``split_index``):
+    dense, bilinear, float32, 1 x 1 x 2049 x 4096, the smallest height past 2^23 pixels at that width with
+    a row beyond.  A smooth image (adjacent pixels ~1e-3 apart) keeps the tolerance near 1e-5 at pos_tol =
+    8 * 2^-24 * 4096 = 2.0e-3 px; the flow is random, about three pixels.  Rows 0, 1, 1023, 1024, 2047 and
+    2048 against the oracle through the row-subset helper; the adjoint once, with a grad_out that is non-zero
+    on those rows only, against float64 autograd on the CPU: all of grad_image, so that nothing lands
+    elsewhere."""
+    N, C, H, W = R.SHAPE_BIG
+    rows = list(R.BIG_ROWS)
+    img, flow = R.smooth_image(H, W), R.big_flow()
+    ptol = R.pos_tol_dense(H, W)
+    tol = R.value_tol(ptol, img, "border")
+    assert R.sensitive(tol, img)
+    grid = R.dense_grid(flow[:, rows], "hw", H, W, np.float32, rows=rows)
+    exp = oracle.grid_sample(img, grid, "bilinear", "border")
+    x, fl = _t(img, device).requires_grad_(True), _t(flow, device)
+    y = F.dense_image_warp(x, fl, "hw", "bilinear", "border")
+    act = y.detach()[:, :, rows].cpu().numpy()
+    err = np.abs(act.astype(np.float64) - exp).max()
+    print("err %.3g of %.3g" % (err, tol))
+    assert err <= tol, (err, tol)
+    g_rows = np.random.default_rng(19).normal(size=(N, C, len(rows), W)).astype(np.float32)
+    g = torch.zeros((N, C, H, W), device=device)
+    g[:, :, rows] = _t(g_rows, device)
+    (gx,) = torch.autograd.grad(y, x, g)
+    gexp = R.adjoint_reference(grid, g_rows, H, W, "bilinear", "border")
+    mass = R.adjoint_mass(R.positions(grid, H, W), g_rows, H, W, "border", ptol)[:, None]
+    gerr = np.abs(gx.cpu().numpy().astype(np.float64) - gexp)
+    gtol = 1e-5 + (2 * ptol + 2.0**-22) * mass
+    print("adjoint err %.3g, largest tolerance %.3g" % (gerr.max(), gtol.max()))
+    assert (gerr <= gtol).all(), (gerr / gtol).max()
+    assert (gexp != 0).sum() > 4 * W and (gx.cpu().numpy()[gexp == 0] == 0).all()
+
+
+def _check_spline(device, c, f, x, order):
+    exp, bound, noise = R.spline_bound(c, f, x, order)
+    act = F.polyharmonic_spline(_t(c, device), _t(f, device), _t(x, device), order).cpu().numpy()
+    err = np.abs(act.astype(np.float64) - exp).max()
+    print("T %d order %d: err %.3g, bound %.3g (noise %.3g)" % (c.shape[1], order, err, bound, noise))
+    assert act.shape == exp.shape and err <= bound, (c.shape[1], order, err, bound)
+    back = F.polyharmonic_spline(_t(c, device), _t(f, device), _t(c, device), order).cpu().numpy()
+    assert np.allclose(back, f, atol=1e-3), np.abs(back - f).max()
+
+
+@pytest.mark.parametrize("order", [1, 2, 3])
+@pytest.mark.parametrize("T", [86, 87, 139, 140])
+def test_spline_solver_regimes(device, T, order):
+    """``spline_solve`` by system size S = T + 3 at I = 2, O = 2 (N = 2, Q = 300: a second, partial workgroup
+    of the evaluation): the augmented matrix takes S (S + 2) 8 + 16 bytes, so T = 86 is the last system in
+    64 KiB of LDS (64,808 bytes), 87 the first behind the function attribute (66,256), 139 the last in LDS
+    (163,600 of 163,776) and 140 the first eliminated in global memory.  Centres on a jittered grid.  Bound:
+    10 x the difference between the oracle's results for two orders of the same centres, floor 2^-23
+    max|expected|; measured on the CPU, that difference is 0 to 7.5e-9 in all twelve cases, so the bound is
+    the floor, 2.8e-7 to 8.6e-7: one float32 ulp of the largest output.  The spline passes through its control points as in
+    test_polyharmonic_spline (1e-3)."""
+    c, f, x = R.spline_case(T, 2, 2, 300, 2, order, T)
+    _check_spline(device, c, f, x, order)
+
+
+def test_spline_gradients_behind_the_attribute(device):
+    """The gradients at T = 87 (the LDS system behind the function attribute), whose adjoint system goes
+    through the solver's ``tail`` rows, against the float64 torch graph at the 1e-3 of
+    test_polyharmonic_spline_gradients."""
+    order = 2
+    c, f, x = R.spline_case(87, 2, 2, 300, 2, order, 87)
+    G = np.random.default_rng(3).normal(size=(2, 300, 2)).astype(np.float32)
+    ref = [torch.from_numpy(a).double().requires_grad_(True) for a in (c, f, x)]
+    (_torch_spline(*ref, order) * torch.from_numpy(G).double()).sum().backward()
+    dev = [_t(a, device).requires_grad_(True) for a in (c, f, x)]
+    (F.polyharmonic_spline(*dev, order) * _t(G, device)).sum().backward()
+    for name, a, b in zip("cfx", dev, ref):
+        err = (a.grad.cpu().double() - b.grad).abs().max() / b.grad.abs().max()
+        assert err < 1e-3, (name, float(err))
+
+
+@pytest.mark.parametrize("T", [125, 126, 315, 316])
+def test_spline_evaluation_lds_sizes(device, T):
+    """``spline_apply_kernel``'s copy of the solution and the centres, (T + 2) 64 8 + 4 T bytes at I = 1, O =
+    64 (Q = 20, N = 2): T = 125 asks for 65,524 bytes, 126 for 66,040 (beyond 64 KiB: behind the function
+    attribute), 315 for 163,564 (the last that fits kSplineLdsCap) and 316 for 164,080, more than a CU has --
+    read from global memory.  Orders 1-3, the bound of the solver test; measured differences between the
+    oracle's two orders of the centres: 0 to 1.1e-6 (order 3 at T = 315, 316), bounds 3.2e-7 to 1.1e-5."""
+    for order in (1, 2, 3):
+        c, f, x = R.spline_case(T, 1, 64, 20, 2, order, T)
+        _check_spline(device, c, f, x, order)
+
+
+@pytest.mark.parametrize("padding", R.PADDINGS)
+@pytest.mark.parametrize("Mp", [138, 140])
+def test_sparse_image_warp_many_control_points(device, Mp, padding):
+    """A sparse warp whose spline system is S = 141 (M' = 138: the solver's last LDS size) and S = 143 (M' =
+    140: global memory), reached through the warp, with the flow, 37 x 29, 130 / 132 points on a jittered
+    grid + ``pinned_boundary_points=2``; the general kernel sums 138 / 140 centres per pixel from
+    (8 M' + 12) bytes of LDS.  Measured pos_tol_sparse 3.2e-3 / 3.7e-3 px (a float32 sum of 140 terms)."""
+    _check_sparse(R.SPARSE_CASES["many-m%d" % Mp], device, padding, ("hw",))

@@ -713,7 +713,9 @@ int pdt_mvn_backward(const void *grad_y, const void *x, int dtype, int64_t A, in
 
 /* ---------------------------------------------------------------------------------------
  * Soft attention (reference _attn.py:200-223): out[r] = sum_t a[r, t] value[r, t], a the softmax
- * over t of the scores with masked frames at -inf; lse[r] its log-sum-exp.  dtype 0 float32,
+ * over t of the scores with masked frames at -inf; lse[r] the row's largest score and lse[R + r] the
+ * log of its sum of exp(score - largest) (kept apart: their sum would round away the second next to
+ * a large |score|).  dtype 0 float32,
  * 1 float64 (accumulated in the same type).
  * desc: PDT_ATTN_DESC_LEN int64, read on the host and copied into the kernel arguments:
  *   [0] nd <= PDT_ATTN_MAX_DIMS row dims, [1] R rows = product of the sizes = G * M, [2] G groups,
@@ -721,7 +723,7 @@ int pdt_mvn_backward(const void *grad_y, const void *x, int dtype, int64_t A, in
  *   broadcast), [4] T, [5] D (0 in the pool forms), [6] Dv, [7 .. 7 + MAX) the row sizes (outermost
  *   first), then per operand slot (query or score, key, value, mask, out / grad_out, grad_query or
  *   grad_score, grad_key, grad_value) MAX row strides, the T stride and the feature stride, in
- *   elements; 0 broadcasts.  lse is (R,) in row order.  mask is bool bytes or NULL (all kept).
+ *   elements; 0 broadcasts.  lse is (2, R) in row order.  mask is bool bytes or NULL (all kept).
  * pdt_attn_dot: scores *scale * query . key (scale: one double in host memory).  pdt_attn_pool: the scores given (score slot).
  * pdt_attn_*_backward: the gradients, recomputing a from lse; grad_key / grad_value are summed
  * over the group.  Masked frames contribute exactly 0.  No float atomics: bitwise reproducible.

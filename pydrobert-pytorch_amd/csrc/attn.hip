@@ -17,13 +17,14 @@
 // value columns.  Four frames' (or four key chunks') loads are issued before their products.  Frames no row of
 // the tile attends to are skipped, keys and values included.  Split
 // spans leave (max, sum, accumulator) partials that one combine pass merges in split order.  The
-// per-row log-sum-exp is kept for the backward.
+// per-row maximum and log of the sum are kept for the backward as two numbers (lse[r], lse[R + r]): their
+// sum in the input's type would round away log(sum) next to a large |maximum|.
 //
 // Large groups of narrow rows (D, Dv <= 32, 16 or more rows per group) take attn_fwd_rows_kernel instead:
 // one thread per row over all of T, the group's rows reading each key and value element together.
 //
 // Backward.  One workgroup per (group, 32 frames) walks every row tile of its group: it recomputes
-// a = exp(score - lse), dP = dout . value and dS = a (dP - delta), delta = rowsum(dout * out) (a
+// a = exp((score - max) - log sum), dP = dout . value and dS = a (dP - delta), delta = rowsum(dout * out) (a
 // separate pass), then sums dK and dV for its frames over the whole group itself -- each element
 // is owned by one thread for the whole walk, so no atomics and a fixed order -- and writes the
 // frames' dQ partial; a combine pass adds the partials in frame order.  The pool forms take the
@@ -99,7 +100,7 @@ template <typename F> struct AttnShared {
   int64_t roff[kAttnRows][NSLOT];
   F sc[kAttnRows][kAttnFrames];  // scores, then probabilities (forward) / a (backward)
   F ds[kAttnRows][kAttnFrames];  // dS (backward)
-  F rm[kAttnRows], rl[kAttnRows], ra[kAttnRows];  // running max, sum, rescale / lse, delta
+  F rm[kAttnRows], rl[kAttnRows], ra[kAttnRows];  // running max, sum, rescale / max, delta, log sum
   uint8_t vm[kAttnRows][kAttnFrames];             // (row, frame) attended
   int fv[kAttnFrames];                            // frame attended by some row of the tile
 };
@@ -279,7 +280,10 @@ __global__ __launch_bounds__(kAttnThreads) void attn_fwd_kernel(AttnArgs a) {
         if (c < d.Dv) o[sh.roff[r][SO] + c * d.fs[SO]] = acc[r][u] / l;  // (0 / 0: an all-masked row is NaN)
       }
     }
-    if (blockIdx.z == 0 && tid < nr) ((F *)a.l)[r0 + tid] = sh.rm[tid] + log(sh.rl[tid]);
+    if (blockIdx.z == 0 && tid < nr) {
+      ((F *)a.l)[r0 + tid] = sh.rm[tid];
+      ((F *)a.l)[d.R + r0 + tid] = log(sh.rl[tid]);
+    }
   } else {
     // partials: m [splits][R], l [splits][R], acc [splits][R][Dv]
     F *pm = (F *)a.ws, *pl = pm + a.splits * d.R, *pa = pl + a.splits * d.R;
@@ -328,12 +332,17 @@ __global__ __launch_bounds__(kAttnThreads) void attn_fwd_rows_kernel(AttnArgs a)
     if (POOL) {
       x = e[t * d.ts[SQ]];
     } else {
+      // the products summed pairwise at distances DMAX / 2 .. 1: the order of the backward's wave_sum over
+      // lanes across D, so that it rebuilds these very scores (bit for bit: a and delta stay consistent)
       const F *kp = k + t * d.ts[SK];
-      x = 0;
+      F pr[DMAX];
 #pragma unroll
-      for (int c = 0; c < DMAX; ++c)
-        if (c < d.D) x += qr[c] * kp[c * d.fs[SK]];
-      x *= scale;
+      for (int c = 0; c < DMAX; ++c) pr[c] = c < d.D ? qr[c] * kp[c * d.fs[SK]] : (F)0;
+#pragma unroll
+      for (int o = DMAX / 2; o > 0; o >>= 1)
+#pragma unroll
+        for (int c = 0; c < o; ++c) pr[c] += pr[c + o];
+      x = pr[0] * scale;
     }
     if (x == neg_inf<F>()) continue;
     if (x > m) {  // (a new maximum: rescale what is summed so far)
@@ -354,7 +363,8 @@ __global__ __launch_bounds__(kAttnThreads) void attn_fwd_rows_kernel(AttnArgs a)
 #pragma unroll
   for (int c = 0; c < DMAX; ++c)
     if (c < d.Dv) o[c * d.fs[SO]] = acc[c] / l;  // (0 / 0: an all-masked row is NaN)
-  ((F *)a.l)[r] = m + log(l);
+  ((F *)a.l)[r] = m;
+  ((F *)a.l)[d.R + r] = log(l);
 }
 
 // merge the split partials in split order: one thread per (row, column)
@@ -379,7 +389,10 @@ template <typename F> __global__ __launch_bounds__(kAttnThreads) void attn_fwd_c
   int64_t off[NSLOT];
   attn_row_offsets(d, r, off);
   ((F *)a.o)[off[SO] + c * d.fs[SO]] = acc / l;
-  if (c == 0) ((F *)a.l)[r] = m + log(l);
+  if (c == 0) {
+    ((F *)a.l)[r] = m;
+    ((F *)a.l)[d.R + r] = log(l);
+  }
 }
 
 // delta[r] = sum_c dout[r, c] * out[r, c]: one wave per row (dout shares out's layout)
@@ -421,6 +434,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_kernel(AttnArgs a) {
 #pragma unroll
       for (int s = 0; s < NSLOT; ++s) sh.roff[tid][s] = off[s];
       sh.rm[tid] = lse[r0 + tid];
+      sh.ra[tid] = lse[d.R + r0 + tid];
       sh.rl[tid] = delta[r0 + tid];
     }
     __syncthreads();
@@ -478,7 +492,7 @@ __global__ __launch_bounds__(kAttnThreads) void attn_bwd_kernel(AttnArgs a) {
         F p = 0, dsv = 0;
         if (lane < nr && j < nt && sh.vm[lane][j]) {
           const F score = POOL ? e[sh.roff[lane][SQ] + (t0 + j) * d.ts[SQ]] : ms * scale;
-          p = exp(score - sh.rm[lane]);
+          p = exp((score - sh.rm[lane]) - sh.ra[lane]);  // (score - max first: exact near a large |max|)
           dsv = p * (mdp - sh.rl[lane]);
         }
         sh.sc[lane][j] = p;

@@ -135,7 +135,7 @@ extern "C" {
 //     that the workspace it is given was filled by a call that keeps its tables (kept_tables below)
 //     and classifies for itself otherwise: the sequence pdt_lev, pdt_lev_classified of earlier
 //     callers keeps its results (the version stays 12)
-int pdt_amd_abi_version(void) { return 13; }
+int pdt_amd_abi_version(void) { return 14; }
 
 int pdt_amd_set_switch(const char *name, int value) {
   if (!name) return PDT_E_ARG;

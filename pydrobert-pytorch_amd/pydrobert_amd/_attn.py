@@ -252,13 +252,14 @@ def _dot_attention_op(
     scale: float,
 ) -> Tuple[torch.Tensor, torch.Tensor]:  # fmt: skip
     """(out, lse): softmax over ``dim`` of ``scale * query . key`` (masked frames at -inf), then the weighted
-    sum of ``value`` over ``dim``; lse is the per-row log-sum-exp the backward reads, in the kernel's row
-    order."""
+    sum of ``value`` over ``dim``; lse is (2, rows), the per-row maximum and log of the sum of exp(score - maximum)
+    that the backward reads, in the kernel's row order (kept apart: their sum would round away the second next
+    to a large |score|)."""
     device = _cabi.require_hip(query, key, value, mask)
     dt = _dtype_code(query, key, value, mask=mask)
     plan, ops = _dot_plan(query, key, value, mask, dim)
     out = torch.empty(plan.out_shape, device=device, dtype=query.dtype)
-    lse = torch.empty((plan.R,), device=device, dtype=query.dtype)
+    lse = torch.empty((2, plan.R), device=device, dtype=query.dtype)
     if plan.R == 0:
         return out, lse
     if plan.T == 0:
@@ -279,7 +280,7 @@ def _dot_attention_op(
 def _(query, key, value, mask, dim, scale):
     _, S = _dot_geometry(query, key, value, mask, dim)
     out_shape = S[:dim] + S[dim + 1:] + [value.shape[-1]]
-    return query.new_empty(out_shape), query.new_empty((_prod(out_shape[:-1]),))
+    return query.new_empty(out_shape), query.new_empty((2, _prod(out_shape[:-1])))
 
 
 @custom_op("pydrobert_amd::dot_attention_backward", mutates_args=())
@@ -341,7 +342,7 @@ def _attention_pool_op(
     dt = _dtype_code(score, value, mask=mask)
     plan, ops = _pool_plan(score, value, mask, dim)
     out = torch.empty(plan.out_shape, device=device, dtype=score.dtype)
-    lse = torch.empty((plan.R,), device=device, dtype=score.dtype)
+    lse = torch.empty((2, plan.R), device=device, dtype=score.dtype)
     if plan.R == 0:
         return out, lse
     if plan.T == 0:
@@ -360,7 +361,7 @@ def _attention_pool_op(
 def _(score, value, mask, dim):
     S = _pool_geometry(score, value, mask, dim)
     out_shape = S[:dim] + S[dim + 1:] + [value.shape[-1]]
-    return score.new_empty(out_shape), score.new_empty((_prod(out_shape[:-1]),))
+    return score.new_empty(out_shape), score.new_empty((2, _prod(out_shape[:-1])))
 
 
 @custom_op("pydrobert_amd::attention_pool_backward", mutates_args=())

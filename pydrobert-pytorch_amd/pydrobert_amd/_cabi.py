@@ -19,8 +19,9 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # on both sides.  The one exception so far: the return and combinatorics entry points were added at 12,
 # because tests/test_random_walk_cpu.py pinned that number; a library built before them is still refused by
 # lib(), with its missing-entry-point message in place of the version one.  13: pdt_pad_variable_backward takes
-# the gradient's dtype (a library of version 12 would read the arguments one place off).
-ABI_VERSION = 13
+# the gradient's dtype (a library of version 12 would read the arguments one place off).  14: the attention
+# entry points' lse holds two numbers per row, (2, R) (a library of version 13 wrote and read R).
+ABI_VERSION = 14
 
 PDT_OK = 0
 PDT_E_ARG = -1

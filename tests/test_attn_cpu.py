@@ -331,3 +331,169 @@ def test_route_leaves_rows_too_wide_for_the_tiles_to_torch():
                           (torch.float64, 7168, True), (torch.float64, 7169, False)):  # fmt: skip
         v = Fake((5, 3, 2), dt)
         assert _attn._hip_route([5, 3], v, None, 0, [Fake((5, 3, 4), dt), v], width) is ok
+
+
+# ----------------------------------------------------------------------------------------------------------
+# the float64 reference, the plan restatement and the case table of tests/_attn_ref.py (test_attn_gpu.py runs
+# the cases on the kernels)
+
+import _attn_ref as R  # noqa: E402
+
+
+def test_reference_matches_torch_formula_and_goldens(gold):
+    """attend_ref / pool_ref against _softmax_pool in float64 (values and gradients), and against the dot-product
+    goldens captured from the reference."""
+    from pydrobert_amd import modules as M
+    from pydrobert_amd._attn import _softmax_pool
+
+    for name in ("spans-dot-64", "spans-pool-64", "neginf-tiles-64", "chunks-key-and-value-expanded",
+                 "chunks-value-broadcast-along-T", "rows-threshold-16-17-strided-64", "walk-pool-flat-64"):
+        def dot(query, key, value, mask, dim, scale):
+            return _softmax_pool((query.unsqueeze(dim) * key).sum(-1) * scale, value, mask, dim)
+
+        out, grads = R.run_case(name, dot, _softmax_pool, torch.float64, "cpu")
+        ref_out, ref_grads = R.expected(name)
+        ok = ~torch.isnan(ref_out)
+        assert torch.allclose(out[ok], ref_out[ok], rtol=1e-12, atol=1e-12), name
+        for n in grads:
+            assert torch.allclose(grads[n], ref_grads[n], rtol=1e-12, atol=1e-12), (name, n)
+    seen = 0
+    for k in range(int(gold["case_n"])):
+        m, ins, mask, spec = load_case(gold, k)
+        if type(m) is not M.DotProductSoftAttention or ins[0].dtype != torch.float64 or m.dim < 0:
+            continue
+        if ins[1].shape[m.dim] == 0:
+            continue  # (T = 0: zeros by convention, not by the formula)
+        out = R.attend_ref(ins[0], ins[1], ins[2], mask, m.dim, m.scale_factor).detach().numpy()
+        exp = gold["case_{}_out".format(k)]
+        fin = ~np.isnan(exp)
+        assert np.array_equal(np.isnan(out), ~fin) and np.allclose(out[fin], exp[fin], rtol=1e-10, atol=1e-10), k
+        seen += 1
+    assert seen > 0
+
+
+def test_dropped_row_variant_takes_the_row_out_of_every_gradient():
+    """The reference used for an all-masked row: its gradients equal those of the same inputs with the row
+    removed, and the row's own gradient is 0."""
+    name = "dead-9-dot"
+    c, x = R.CASES[name], R.build_inputs(name)
+    (g0, m0), = np.argwhere(x["dead"])
+    _, grads = R.expected(name)
+    keep = [m for m in range(c["M"]) if m != m0]
+    q = torch.from_numpy(x["q"][g0, keep]).requires_grad_(True)
+    k = torch.from_numpy(x["k"][:, g0].copy()).requires_grad_(True)  # (T, 1, D)
+    v = torch.from_numpy(x["v"][:, g0].copy()).requires_grad_(True)
+    out = R.attend_ref(q, k, v, torch.from_numpy(x["mask"][:, g0][:, keep]), 0, x["scale"])
+    gq, gk, gv = torch.autograd.grad(out, (q, k, v), torch.from_numpy(x["gout"][g0, keep]))
+    assert torch.allclose(grads["k"][:, g0], gk, rtol=1e-12, atol=1e-12)
+    assert torch.allclose(grads["v"][:, g0], gv, rtol=1e-12, atol=1e-12)
+    assert torch.allclose(grads["q"][g0, keep], gq, rtol=1e-12, atol=1e-12)
+    assert bool((grads["q"][g0, m0] == 0).all())
+
+
+def _lib():
+    import __graft_entry__ as g
+    from pydrobert_amd import _cabi
+
+    if not os.path.exists(_cabi.LIB_PATH):
+        g.build()
+    return _cabi.lib()
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_plan_restatement_matches_the_library(name):
+    """plan_of against pdt_attn_workspace_bytes for every case and all four kinds (no launch: no GPU needed).
+    Equal workspace sizes pin the forward's splits and its choice of the rows kernel, and the backward's
+    frame chunks."""
+    lib = _lib()
+    c = R.CASES[name]
+    G, M = R.plan_shape(c)
+    for dt, esz in ((0, 4), (1, 8)):
+        for kind, code in R.KINDS.items():
+            pool = kind.startswith("pool")
+            D = 0 if pool else max(1, c["D"])
+            p = R.plan_of(G, M, c["T"], D, c["Dv"], esz, kind)
+            desc = _desc(R=G * M, G=G, M=M, T=c["T"], D=D, Dv=c["Dv"], sizes=(G, M))
+            assert lib.pdt_attn_workspace_bytes(desc, dt, code) == p["ws_bytes"], (kind, esz, p)
+            if not kind.endswith("bwd"):
+                assert (p["ws_bytes"] == 0) == (p["splits"] == 1)
+                if c["T"] > 32 and G * p["tiles"] * max(1, p["zcols"]) < 512:
+                    assert (p["ws_bytes"] == 0) == bool(p["rows_form"])  # (few workgroups: only the rows form is unsplit)
+
+
+def test_rows_per_tile_by_element_size_decides_the_spans():
+    """Shapes where the row tiles per group (rows per tile by LDS: the bytes of a row, so the element size)
+    decide how T is split: the workspace pins the rows per tile."""
+    lib = _lib()
+    for G, M, T, D, Dv, esz, form in R.PLAN_ONLY:
+        p = R.plan_of(G, M, T, D, Dv, esz, "dot")
+        assert {k: p[k] for k in form} == form, p
+        other = R.plan_of(G, -(-M // min(8, M)), T, 1, Dv, esz, "dot")  # (the spans if 8 rows fitted a tile)
+        assert other["splits"] != p["splits"], "the shape is sensitive to the rows per tile"
+        desc = _desc(R=G * M, G=G, M=M, T=T, D=D, Dv=Dv, sizes=(G, M))
+        assert lib.pdt_attn_workspace_bytes(desc, 0 if esz == 4 else 1, 0) == p["ws_bytes"], (G, M, T, D, esz)
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_case_has_the_plan_form_it_is_named_for(name):
+    c = R.CASES[name]
+    G, M = R.plan_shape(c)
+    esz = 4 if c["dtype"] == "float32" else 8
+    assert c["form"], "every case names a form"
+    for side, claim in c["form"].items():
+        p = R.plan_of(G, M, c["T"], c["D"], c["Dv"], esz, c["route"] + ("_bwd" if side == "bwd" else ""))
+        assert {k: p[k] for k in claim} == claim, (side, p)
+    assert max(c["G"] * c["M"] * max(c["D"], c["Dv"]), c["T"] * c["G"] * max(c["D"], c["Dv"])) <= 2.4e6  # (small tensors)
+
+
+@pytest.mark.parametrize("name", list(R.CASES))
+def test_case_mask_is_what_the_case_claims(name):
+    """Each mask recipe's claims, from the mask alone; an all-masked row only in the cases named for one, and
+    one at most.  The spoiled inputs are non-finite exactly where no row (pool score: not this row) attends."""
+    c, x = R.CASES[name], R.build_inputs(name)
+    dead = R.check_mask(c["mask"], x["mask"], c["T"], c["G"], c["M"])
+    assert np.array_equal(dead, x["dead"]) and dead.sum() <= 1
+    assert bool(dead.any()) == (c["mask"] in ("dead_row", "spans"))
+    if c["bad"]:
+        unseen = ~x["mask"].any(2)
+        assert unseen.any() and np.array_equal(np.isnan(x["v_bad"]).all((2, 3)), unseen)
+        if c["route"] == "dot":
+            assert np.array_equal(np.isinf(x["k_bad"]).all((2, 3)), unseen)
+        else:
+            assert np.array_equal(~np.isfinite(x["e_bad"]), ~x["mask"])
+    if c["neginf"]:
+        seen = x["e"] if x["mask"] is None else np.where(x["mask"], x["e"], 0.0)
+        assert np.isneginf(seen).any() and np.isfinite(np.where(np.isneginf(seen), -np.inf, x["e"])).any(0).all()
+        kept = np.isfinite(x["e"]) & (True if x["mask"] is None else x["mask"])
+        assert kept.any(0).all(), "every row keeps a finite score"
+    if c["profile"] is not None and x["mask"] is None:  # (the 32-frame tiles' maxima follow the trend in every row)
+        e = R.scores_of(name)
+        tile_max = [e[a:a + 32].max(0) for a in range(0, c["T"], 32)]
+        assert len(tile_max) == 3
+        for a, b in zip(tile_max, tile_max[1:]):
+            assert bool({"rising": b > a + 1, "falling": b < a - 1, "flat": (b == a) & (b == R.flat_score(c))}[c["profile"]].all())
+
+
+@pytest.mark.parametrize("name", [n for n, c in R.CASES.items() if c["measured"]])
+def test_measured_tolerances_follow_the_rule(name):
+    """The wide or long cases (D, Dv or T above 300) and the shifted ones: every recorded bound is the suite's
+    or lies in [4, 16] x err32 (the float32 formula's own error on the case's inputs, recomputed here) and is
+    not below the suite's; every bound is under 1 % of the median |reference| of its tensor (over its non-zero
+    entries: gradients are exactly 0 at masked frames)."""
+    c = R.CASES[name]
+    ref_out, ref_grads = R.expected(name)
+    refs = dict(ref_grads, out=ref_out[~torch.isnan(ref_out)])
+    assert set(c["tol"]) <= set(refs)
+    err32 = R.formula32_error(name) if c["dtype"] == "float32" else None
+    for n, ref in refs.items():
+        suite, atol = R.bound(name, n)
+        if err32 is not None:
+            print("{} {}: err32 {:.3e}, 8 x err32 {:.3e}, bound {:.1e}".format(name, n, err32[n], 8 * err32[n], atol))
+            if atol != suite:
+                assert atol > suite and 4 * err32[n] <= atol <= 16 * err32[n], (n, err32[n], atol)
+            else:
+                assert 8 * err32[n] <= suite, (n, err32[n], "needs a measured bound")
+        else:
+            assert atol == suite  # (float64: no case needs more than the suite's bound)
+        mag = ref.abs()[ref != 0]
+        assert atol < 0.01 * float(mag.median()), (n, atol, float(mag.median()))

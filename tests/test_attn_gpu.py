@@ -1,13 +1,22 @@
 """GPU: the attention modules on the HIP kernels -- the goldens (captured from the reference), random
 broadcast patterns and strided inputs against the reference's formula in float64, gradcheck of both
-operators, long sequences and wide features (split T), determinism, streams, no host synchronisation, and
-the route the modules take."""
+operators, determinism, streams, no host synchronisation, and the route the modules take.
+
+The sweeps, ``test_long_and_wide_against_formula`` and the decode shape have few groups, so their forward is
+always split into spans of one 32-frame tile (with the combine pass); ``test_large_narrow_groups_against_formula``
+runs the one-thread-per-row forward below one workgroup of rows.  Every other form the host plan can take is
+reached by a named case of ``tests/_attn_ref.py`` (float64 formula, plan restatement, masks and tolerances
+checked in ``test_attn_cpu.py``), run by the tests at the end of this file: several tiles per workgroup with
+and without the combine, rows per tile set by LDS, value column blocks, key loop tails, the rows kernel's
+instances and workgroups, the backward's frame chunks, empty spans, non-finite masked frames on every route,
+scores at -inf, an all-masked row in a group, and shifted scores."""
 import copy
 
 import numpy as np
 import pytest
 import torch
 
+import _attn_ref as R
 from test_attn_cpu import check_case, cosine_attention, load_case, upstream  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -327,3 +336,114 @@ def test_compile_on_device():
     g = torch.randn(16, 8, 48, device=DEV)
     for a, b in zip(_run(comp, q, k, v, mask, g), _run(m, q, k, v, mask, g)):
         assert torch.allclose(a, b, atol=1e-6)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# the named cases of tests/_attn_ref.py: output, NaN pattern and every gradient against the float64 formula
+
+
+def _hip_case(name, spoiled=False):
+    """Runs a case on the kernels (the operators called directly, the mask as it is) and compares."""
+    from pydrobert_amd import _attn
+
+    c = R.CASES[name]
+    dtype = torch.float32 if c["dtype"] == "float32" else torch.float64
+    out, grads = R.run_case(name, _attn.dot_attention, _attn.attention_pool, dtype, DEV, spoiled=spoiled, dropped=False)
+    R.compare(name, out, grads)
+    return out, grads
+
+
+@pytest.mark.parametrize("name", R.cases_of("walk"))
+def test_forward_walks_several_tiles_per_workgroup(name):
+    """attn_fwd_kernel over more than one 32-frame tile per workgroup: the online-softmax carry (m_old, alpha,
+    the rescaled sum and accumulators).  1100 groups: splits 1, span 96, tiles of 32 + 32 + 6 frames, with scores
+    rising (a new maximum per tile, alpha < 1), falling (alpha = 1), flat at -1e4, the first tile masked for a
+    third of the rows (m_old = -inf), the middle tile masked for all (skipped) and one all-masked row (NaN).
+    300 groups over T = 250: 4 spans of 64 (the last of 58), the carry and the combine together.  The control
+    (130 groups of 9 rows) has one tile per span."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("lds"))
+def test_rows_per_tile_set_by_lds(name):
+    """attn_rows_per_tile below 8 by LDS with several row tiles: forward rt 7 (7 + 2 rows) and rt 1; a backward
+    whose tile (rt 7 at 56000 bytes, rt 3) differs from the forward's, dK / dV accumulated across its tiles;
+    the pool backward at rt 7.  Causal masks: every row of a tile has its own limit."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("cols"))
+def test_value_column_blocks(name):
+    """grid.z over value columns: Dv 1024 / 1025 / 1300 / 2049 (1 / 2 / 2 / 3 blocks, the last partial) with
+    split T, float32 and float64, dot and pool; Dv 1300 over 600 groups: two blocks, unsplit."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("keys"))
+def test_key_loop_tails(name):
+    """The forward's key loop (four loads of 64 in flight: D strided by 256) and the backward's (by 64) at
+    D 1, 63, 64, 65, 255, 256, 257, 300 and 513."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("rows"))
+def test_rows_kernel_forms(name):
+    """attn_fwd_rows_kernel: 600 rows in three workgroups (the last partial, a wave across the group boundary,
+    an all-masked row), the 16-row threshold, the 16 and 32 instances (Dv 17, D 32, D = Dv = 1), dot and pool,
+    a strided query, T = 2000; M = 15 and D = 33 take the tiles (controls)."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("chunks"))
+def test_backward_frame_chunk_forms(name):
+    """The backward at T 1, 31, 32 (one chunk: dQ written directly), 33, 64, 65 (attn_gq_combine_kernel), groups
+    of 1, 8, 9 and 17 rows, R = 1, 3, 5 rows for the delta kernel's partial workgroup, dot and pool, a value
+    broadcast along T, a key and value expanded by the caller."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("spans"))
+def test_split_partials_with_empty_spans(name):
+    """Split partials of rows that attend nothing in the first span, nothing in the last span, and nothing at
+    all (NaN through the combine): outputs, the NaN pattern and the gradients of the rows that attend."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("bad"))
+def test_masked_non_finite_frames_in_every_route(name):
+    """The deviation (inf keys and NaN values in masked frames reach nothing) in a group of 9 rows that mask
+    differently, the rows kernel, the pool route (a non-finite score at every masked (row, frame) too),
+    splits == 1 and span > 32.  A key or value is shared by its group, so the spoiled frames are those no row
+    of the group attends.  Reference: the float64 formula on the clean inputs."""
+    out, grads = _hip_case(name, spoiled=True)
+    c, x = R.CASES[name], R.build_inputs(name)
+    assert bool(torch.isfinite(out).all())
+    unseen = torch.from_numpy(~x["mask"].any(2)).to(DEV)
+    assert bool((grads["v"][unseen] == 0).all())
+    if c["route"] == "dot":
+        assert bool((grads["k"][unseen] == 0).all())
+    else:
+        assert bool((grads["e"][torch.from_numpy(~x["mask"]).to(DEV)] == 0).all())
+
+
+@pytest.mark.parametrize("name", R.cases_of("neginf"))
+def test_pool_scores_at_minus_infinity(name):
+    """attention_pool with -inf in the score itself, unmasked (the x == -inf branches of the tile and the rows
+    kernel): equal to the formula, grad_score exactly 0 there and finite elsewhere."""
+    out, grads = _hip_case(name)
+    e = torch.from_numpy(R.build_inputs(name)["e"].copy()).to(DEV)
+    assert bool((grads["e"][torch.isneginf(e)] == 0).all()) and bool(torch.isfinite(grads["e"]).all())
+
+
+@pytest.mark.parametrize("name", R.cases_of("dead"))
+def test_all_masked_row_leaves_its_group_alone(name):
+    """One row of a group of 9 / 70 (rows kernel forward) masked everywhere: its output is NaN, every gradient
+    is finite, its own dQ (dE) is exactly 0, and dK / dV equal the reference computed without that row."""
+    _hip_case(name)
+
+
+@pytest.mark.parametrize("name", R.cases_of("shift"))
+def test_shifted_scores(name):
+    """Every score of a row shifted by 0, 10 and 100 (float32, tiles and rows forward): the backward rebuilds
+    a = exp(score - lse) from one stored float.  Bounds: max(suite, 8 x the float32 formula's own error)."""
+    _hip_case(name)

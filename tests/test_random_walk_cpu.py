@@ -28,10 +28,10 @@ def test_symbols_exported_and_declared(lib):
         assert hasattr(lib, name) and name in _cabi.SIGNATURES and name + "(" in header
 
 
-def test_abi_version_is_13(lib):
+def test_abi_version_is_14(lib):
     from pydrobert_amd import _cabi
 
-    assert _cabi.ABI_VERSION == 13 and lib.pdt_amd_abi_version() == 13
+    assert _cabi.ABI_VERSION == 14 and lib.pdt_amd_abi_version() == 14
 
 
 def test_empty_batches_and_bad_arguments_without_gpu(lib):

@@ -1,7 +1,7 @@
 import sys, os, time
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "pydrobert-pytorch_amd"))
 import torch
-from pydrobert_amd import functional as F, _decoding as D
+from pydrobert_amd import functional as F, _step as D
 dev = torch.device("cuda:0")
 N, K, V, S = 1024, 16, 1000, 100
 g = torch.Generator(device=dev).manual_seed(4)

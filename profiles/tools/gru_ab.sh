@@ -1,6 +1,6 @@
 #!/bin/bash
 # The fused step kernel inside the GRU-LM loop (profiles/tools/gru_loop.py) under rocprofv3, per library variant
-# (VARIANTS="default adv_ph1 ..."; profiles/tools/build_var.sh): the kernel's own average duration.
+# (VARIANTS="default ..."; profiles/tools/build_var.sh): the kernel's own average duration.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for v in ${VARIANTS:-default}; do
   if [ $v = default ]; then unset PDT_AMD_LIB; else export PDT_AMD_LIB=$PWD/pydrobert-pytorch_amd/csrc/build/variants/$v/lib.so; fi

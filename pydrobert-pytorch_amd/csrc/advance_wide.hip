@@ -7,8 +7,8 @@
 // index, so "first" is well defined) -- then the K winners are ranked by counting.  The candidates
 // are never materialised: every pass re-evaluates them from the inputs (L2 resident: K' * V floats
 // per element).  Semantics: reference _decoding.py:41-155 and :636-934; ties as in the wave forms
-// (beam_advance.hip), i.e. to the lowest flat index.
-#include "advance_args.hpp"
+// (beam_advance.hip, ctc_advance.hip), i.e. to the lowest flat index.
+#include "step_launch.hpp"
 #include "wave_select.hpp"
 
 namespace pdt {
@@ -195,20 +195,17 @@ __global__ void __launch_bounds__(kWideThreads) beam_advance_wide_kernel(const B
   }
 }
 
-static int wide_launch(const void *kern, size_t smem) {
+template <class Kernel>
+static int wide_launch(Kernel *kern, size_t smem) {
   if (smem > 160 * 1024) return PDT_E_TOO_LONG;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
-  return PDT_OK;
+  return set_lds(kern, smem);
 }
 
 int launch_beam_advance_wide(BeamAdvArgs a, hipStream_t stream) {
   if ((int64_t)a.Kp * a.V >= (1ll << 31)) return PDT_E_TOO_LONG;
   const int K = (int)min((int64_t)a.W, (int64_t)a.Kp * a.V);
   const size_t smem = (WideSel::bytes(K) + (size_t)a.W * 12 + 15) & ~(size_t)15;
-  if (int rc = wide_launch(reinterpret_cast<const void *>(beam_advance_wide_kernel), smem)) return rc;
+  if (int rc = wide_launch(beam_advance_wide_kernel, smem)) return rc;
   hipLaunchKernelGGL(beam_advance_wide_kernel, dim3((unsigned)a.N), dim3(kWideThreads), smem, stream, a);
   return (int)hipGetLastError();
 }
@@ -363,7 +360,7 @@ int launch_ctc_advance_wide(CtcAdvArgs a, hipStream_t stream) {
   if ((int64_t)a.Kp * (a.V + 1) >= (1ll << 31)) return PDT_E_TOO_LONG;
   const int K = (int)min((int64_t)a.W, (int64_t)a.Kp * (a.V + 1));
   const size_t smem = (WideSel::bytes(K) + (size_t)a.Kp * (24 + 4 * kWideWaves) + (size_t)a.W * 16 + 15) & ~(size_t)15;
-  if (int rc = wide_launch(reinterpret_cast<const void *>(ctc_advance_wide_kernel), smem)) return rc;
+  if (int rc = wide_launch(ctc_advance_wide_kernel, smem)) return rc;
   hipLaunchKernelGGL(ctc_advance_wide_kernel, dim3((unsigned)a.N), dim3(kWideThreads), smem, stream, a);
   return (int)hipGetLastError();
 }

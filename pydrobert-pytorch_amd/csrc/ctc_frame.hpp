@@ -1,5 +1,5 @@
 // One frame of CTC prefix beam search at wave level (shared by the fused search kernel in
-// ctc_search.hip and the step-function kernel in beam_advance.hip).  See ctc_search.hip for
+// ctc_search.hip and the step-function kernel in ctc_advance.hip).  See ctc_search.hip for
 // the design notes.
 #pragma once
 #include "wave_select.hpp"
@@ -104,7 +104,7 @@ struct DenseCtx {
   int lists_ready;       // the per-prefix lists are in L.tl_tok / L.tl_p already (built by the caller's waves)
   // Instead of whole rows of extension probabilities: the K' x K' entries the frame reads besides
   // the lists -- etab[k * etab_stride + j] = ext[k, clamp(last token of prefix j)] (a caller that
-  // forms each row on the fly and keeps only its list: beam_advance.hip, the n-gram fused step)
+  // forms each row on the fly and keeps only its list: ctc_advance.hip, the n-gram fused step)
   const float *etab = nullptr;
   int etab_stride = 0;
   // the same history as 16-bit tokens (a caller that keeps its own, narrower copy between frames)

@@ -13,7 +13,7 @@
 // (The timing experiments of round 3 -- a phase run twice with identical results, phases skipped --
 // are described in EXPERIMENTS.md section 9.16; their macro families left the file in round 4.  What
 // stays is the per-phase stamp build, -DPDT_LM_STAMPS.)
-#include "advance_args.hpp"
+#include "step_launch.hpp"
 #include "ctc_frame.hpp"
 #include "row_reduce.hpp"
 
@@ -433,8 +433,7 @@ static size_t plan_lm_frame(CtcLmAdvArgs &A) {
     return frame + (size_t)nw * PDT_SURV_CAP * 8 + (size_t)((Kp * Kp + 3) & ~3) * 4 + (size_t)nw * A.row_floats * 4 +
            (size_t)Kp * kLmMaxOrder * 4 + (size_t)width * 8;  // + the context table, the leaders, two slot lists
   };
-  int nw = 1;
-  while (nw < 8 && nw * 2 <= a.Kp) nw *= 2;
+  int nw = step_waves(a.Kp);
   while (nw > 1 && lds_of(nw) > 40 * 1024) nw >>= 1;
   const size_t smem = lds_of(nw);
   if (smem > 160 * 1024) return 0;
@@ -568,11 +567,7 @@ extern "C" int pdt_ctc_lookup_lm_search(
   const size_t smem = plan_lm_frame(A);
   if (smem == 0) return PDT_E_TOO_LONG;
   auto kern = hb == 2 ? ctc_lm_search_kernel<int16_t> : ctc_lm_search_kernel<int64_t>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(kern, smem)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)N), dim3(64 * a.waves_per_wg), smem, hs, A, st[0], st[1], probs, p_st,
                      p_sn, p_sv, (int)n_frames);
   const int rc = (int)hipGetLastError();

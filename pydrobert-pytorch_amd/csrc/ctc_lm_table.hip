@@ -598,11 +598,7 @@ ctc_lm_table_kernel(const LmTabArgs A, const LmTabLayout ly) {
 template <int NR, int WC = -1>
 static int launch_lm_table(const LmTabArgs &A, const LmTabLayout &ly, hipStream_t stream) {
   const size_t smem = (size_t)ly.utt_bytes;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ctc_lm_table_kernel<NR, WC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(ctc_lm_table_kernel<NR, WC>, smem)) return rc;
   hipLaunchKernelGGL((ctc_lm_table_kernel<NR, WC>), dim3((unsigned)A.c.N), dim3(256), smem, stream, A, ly);
   return (int)hipGetLastError();
 }

@@ -436,11 +436,7 @@ void ctc_rowreg_plan(int V, int W, int32_t *plan5) {
 template <int NR, int NF, int P, int WC = -1>
 static int launch_rowreg(const CtcArgs &a, const RowregLayout &rl, hipStream_t stream) {
   const size_t smem = (size_t)rl.utt_bytes * rl.utt_per_wg;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ctc_rowreg_kernel<NR, NF, P, WC>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(ctc_rowreg_kernel<NR, NF, P, WC>, smem)) return rc;
   const unsigned grid = (unsigned)((a.N + rl.utt_per_wg - 1) / rl.utt_per_wg);
   hipLaunchKernelGGL((ctc_rowreg_kernel<NR, NF, P, WC>), dim3(grid), dim3(256), smem, stream, a, rl);
   return (int)hipGetLastError();

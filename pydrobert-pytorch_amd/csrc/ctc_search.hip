@@ -770,11 +770,7 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
 template <int P, int NT = -1, bool INREG = (P == 1), bool GROW = false, int WC = -1, int VC = -1, bool PAIR = false>
 static int launch_ctc_search_p(const CtcArgs &a, const RingLayout &rl, hipStream_t stream) {
   const size_t smem = (size_t)rl.utt_bytes * rl.utt_per_wg;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR>, smem)) return rc;
   const unsigned grid = (unsigned)((a.N + rl.utt_per_wg - 1) / rl.utt_per_wg);
   hipLaunchKernelGGL((ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR>), dim3(grid), dim3(64 * (P + 1) * rl.utt_per_wg), smem,
                      stream, a, rl);

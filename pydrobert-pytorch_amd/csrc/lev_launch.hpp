@@ -9,15 +9,6 @@ namespace pdt {
 
 struct BitparArgs;  // bitpar_classify.hpp
 
-// Dynamic LDS beyond `cap` has to be asked for before the launch.  (The cap is the caller's: the
-// cell-by-cell kernels size their workgroups against a soft cap of their own.)
-template <class Kernel>
-static inline int set_lds(Kernel *kern, size_t smem, size_t cap = 64 * 1024) {
-  if (smem <= cap) return 0;
-  return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)smem);
-}
-
 // lev_skewed.hip, lev_rowsync.hip: the cell-by-cell recurrences
 int launch_lev_skewed(LevArgs a, hipStream_t stream);
 int launch_lev_rowsync(LevArgs a, bool exact, hipStream_t stream);

@@ -16,6 +16,15 @@
 
 namespace pdt {
 
+// Dynamic LDS beyond `cap` has to be asked for before the launch.  (The cap is the caller's: the
+// cell-by-cell string kernels size their workgroups against a soft cap of their own.)
+template <class Kernel>
+static inline int set_lds(Kernel *kern, size_t smem, size_t cap = 64 * 1024) {
+  if (smem <= cap) return 0;
+  return (int)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)smem);
+}
+
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 
 // value of lane-1 (lane 0 receives `first`).  One v_mov_b32_dpp wave_shr:1.

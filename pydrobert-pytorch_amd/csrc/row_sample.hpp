@@ -1,5 +1,5 @@
 // One row of scores through a wave: its (maximum, log-sum-exp) and the sampling rule of every random-walk
-// kernel (random_walk.hip).  BeamSearch's step kernels and the row-stats kernel (beam_step.hip) use the same
+// kernel (random_walk.hip).  BeamSearch's step kernels (beam_step.hip) and the row-stats kernel (beam_search_table.hip) use the same
 // row_log_softmax_stats, so a row's statistics have the same bits whichever kernel forms them.
 #pragma once
 #include "wave_select.hpp"

@@ -210,11 +210,7 @@ int pdt_ctc_greedy_search(const float *logits, int64_t T, int64_t N, int64_t V, 
   a.is_probs = is_probs; a.max_out = max_out; a.paths = paths; a.pa_st = pa_st; a.pa_sn = pa_sn;
   a.out_lens = out_lens; a.nw = seq_waves(T);
   auto kern = V <= 8 * PDT_WAVE ? ctc_greedy_kernel<8> : ctc_greedy_kernel<16>;
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(kern, smem)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)N), dim3(64 * a.nw), smem, (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }

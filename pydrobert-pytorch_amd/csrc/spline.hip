@@ -169,11 +169,7 @@ static int spline_apply(const float *c, const double *wv, const float *x, int64_
                        (int)Q, order, out);
     return (int)hipGetLastError();
   }
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(spline_apply_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(spline_apply_kernel<true>, smem)) return rc;
   hipLaunchKernelGGL(spline_apply_kernel<true>, grid, dim3(256), smem, stream, c, wv, x, (int)T, (int)I, (int)O,
                      (int)Q, order, out);
   return (int)hipGetLastError();
@@ -233,11 +229,7 @@ int spline_solve(const float *c, const float *f, const float *tail, int64_t N, i
                                       (((size_t)N * S * O * (sizeof(double) + sizeof(float)) + 63) & ~(size_t)63));
     smem = 16;
   }
-  if (smem > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(spline_solve_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = set_lds(spline_solve_kernel, smem)) return rc;
   hipLaunchKernelGGL(spline_solve_kernel, dim3((unsigned)N), dim3(256), smem, stream, c, f, tail,
                      (int)T, (int)I, (int)O, order, reg, wv, gmat);
   return (int)hipGetLastError();

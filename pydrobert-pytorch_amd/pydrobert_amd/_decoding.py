@@ -1,528 +1,27 @@
 """Beam-search decoding on MI355X.
 
 Host-side mirror of the reference's ``_decoding.py`` for the operators on the hot path:
-``CTCPrefixSearch`` / ``ctc_prefix_search_advance`` and ``BeamSearch`` /
-``beam_search_advance``.  The step functions and the fused CTC search run in
-``csrc/beam_advance.hip`` and ``csrc/ctc_search.hip`` through the C ABI
-(``include/pdt_amd.h``); the Modules keep the reference's control flow around a
-user-supplied language model.
+``ctc_prefix_search`` / ``CTCPrefixSearch`` and ``BeamSearch``, with the caches of the n-gram
+tables they search over.  The fused CTC search runs in ``csrc/ctc_search.hip``, BeamSearch's
+iterations in ``csrc/beam_step.hip`` and ``csrc/beam_search_table.hip``, through the C ABI
+(``include/pdt_amd.h``); the Modules keep the reference's control flow around a user-supplied
+language model.  The step functions are in ``_step.py``, greedy search and sequence
+log-probabilities in ``_seqops.py``, the random walks in ``_walk.py``.
 """
 import math
 import weakref
-from typing import Any, Dict, Optional, Tuple
+from typing import Dict, Optional, Tuple
 
 import torch
-from torch.library import custom_op, register_autograd
+from torch.library import custom_op
 
 from . import _cabi, argcheck, config, switches
 from ._lm import ExtractableSequentialLanguageModel, LookupLanguageModel, MixableSequentialLanguageModel
+from ._step import _ctc_step_with_lm_scores, _f32, _i64, ctc_prefix_search_advance
 
-__all__ = [
-    "BeamSearch",
-    "CTCGreedySearch",
-    "CTCPrefixSearch",
-    "RandomWalk",
-    "SequenceLogProbabilities",
-    "beam_search_advance",
-    "ctc_greedy_search",
-    "ctc_prefix_search",
-    "ctc_prefix_search_advance",
-    "random_walk_advance",
-    "sequence_log_probs",
-]
+__all__ = ["BeamSearch", "CTCPrefixSearch", "ctc_prefix_search"]
 
 MAX_CTC_WIDTH = 32
-
-
-def _f32(t: torch.Tensor) -> torch.Tensor:
-    if t.requires_grad:
-        t = t.detach()
-    return t if t.dtype == torch.float else t.float()
-
-
-def _i64(t: torch.Tensor) -> torch.Tensor:
-    if t.requires_grad:
-        t = t.detach()
-    return t if t.dtype == torch.long else t.long()
-
-
-def _beam_search_advance_impl(
-    log_probs_t: torch.Tensor,
-    width: int,
-    log_probs_prev: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_lens: Optional[torch.Tensor],
-    grows: Optional[bool] = None,
-) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    # `grows`: the caller already knows whether some path is as long as the history (y_next
-    # then has one row more, reference :133-135), which saves the read-back of max(y_prev_lens);
-    # None = find out here
-    if log_probs_t.dim() != 3:
-        raise RuntimeError("log_probs_t must be 3 dimensional")
-    N, Kp, V = log_probs_t.shape
-    if width < 1:
-        raise RuntimeError("Expected width to be >= 1, got {}".format(width))
-    if log_probs_prev.shape != (N, Kp):
-        raise RuntimeError(
-            "Expected log_probs_prev to be of shape {}, got {}".format((N, Kp), tuple(log_probs_prev.shape))
-        )
-    if y_prev.dim() != 3:
-        raise RuntimeError("y_prev must be 3 dimensional")
-    if y_prev.shape[1:] != (N, Kp):
-        raise RuntimeError(
-            "Expected the last two dimensions of y_prev to be {}, got {}".format(
-                (N, Kp), tuple(y_prev.shape[1:])
-            )
-        )
-    S = y_prev.size(0)
-    if y_prev_lens is not None and y_prev_lens.shape != (N, Kp):
-        raise RuntimeError(
-            "Expected y_prev_lens to have shape {}, got {}".format((N, Kp), tuple(y_prev_lens.shape))
-        )
-    device = _cabi.require_hip(log_probs_t, log_probs_prev, y_prev, y_prev_lens)
-    lpt, lpp, yp = _f32(log_probs_t), _f32(log_probs_prev), _i64(y_prev)
-    ypl = None if y_prev_lens is None else _i64(y_prev_lens)
-    grow = True
-    if grows is not None:
-        grow = grows
-    elif ypl is not None and N * Kp:
-        # :133-135 don't make y bigger unless we have to; :139-140 -- the reference's own host read
-        # (`y_prev_lens.max()`), as one small kernel that raises a word in pinned host memory
-        report = _cabi.host_report(device)
-        with _cabi.on_device(device):
-            rc = _cabi.lib().pdt_lens_reach(
-                _cabi.ptr(ypl), ypl.stride(0), ypl.stride(1), N, Kp, S, report.ptr, _cabi.stream_ptr(device)
-            )
-            if rc:
-                report.disarm()
-                _cabi.check(rc, "pdt_lens_reach")
-        seen = report.wait()
-        if S:
-            grow = bool(seen & 1)
-        elif seen & 2:
-            raise RuntimeError("Invalid lengths for t=0")
-    S_out = S + (1 if grow else 0)
-    with _cabi.on_device(device):
-        y_next = torch.empty((S_out, N, width), device=device, dtype=torch.long)
-        y_next_lens = torch.empty((N, width), device=device, dtype=torch.long)
-        next_src = torch.empty((N, width), device=device, dtype=torch.long)
-        lp_next = torch.empty((N, width), device=device, dtype=torch.float)
-        if N and V:
-            rc = _cabi.lib().pdt_beam_search_advance(
-                _cabi.ptr(lpt), lpt.stride(0), lpt.stride(1), lpt.stride(2), N, Kp, V, int(width),
-                _cabi.ptr(lpp), lpp.stride(0), lpp.stride(1),
-                _cabi.ptr(yp), S, yp.stride(0), yp.stride(1), yp.stride(2),
-                _cabi.ptr(ypl), 0 if ypl is None else ypl.stride(0), 0 if ypl is None else ypl.stride(1),
-                S_out, _cabi.ptr(y_next), _cabi.ptr(y_next_lens), _cabi.ptr(lp_next),
-                _cabi.ptr(next_src), _cabi.stream_ptr(device),
-            )  # fmt: skip
-            _cabi.check(rc, "pdt_beam_search_advance")
-    return y_next, y_next_lens, lp_next.to(log_probs_t.dtype), next_src
-
-
-@custom_op("pydrobert_amd::beam_search_advance", mutates_args=())
-def _beam_search_advance_op(
-    log_probs_t: torch.Tensor,
-    width: int,
-    log_probs_prev: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_lens: Optional[torch.Tensor],
-    grows: Optional[bool] = None,
-) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    return _beam_search_advance_impl(log_probs_t, width, log_probs_prev, y_prev, y_prev_lens, grows)
-
-
-@_beam_search_advance_op.register_fake
-def _(log_probs_t, width, log_probs_prev, y_prev, y_prev_lens, grows=None):
-    N = log_probs_t.shape[0]
-    S = y_prev.shape[0]
-    if grows is not None:
-        S_out = S + (1 if grows else 0)
-    elif y_prev_lens is not None:  # data dependent: S or S + 1 (:133-135)
-        S_out = torch.library.get_ctx().new_dynamic_size()
-    else:
-        S_out = S + 1
-    return (
-        y_prev.new_empty((S_out, N, width), dtype=torch.long),
-        y_prev.new_empty((N, width), dtype=torch.long),
-        log_probs_t.new_empty((N, width)),
-        y_prev.new_empty((N, width), dtype=torch.long),
-    )
-
-
-def _beam_search_advance_setup(ctx, inputs, output):
-    log_probs_t, _, log_probs_prev = inputs[:3]
-    y_next, y_next_lens, lp_next, next_src = output
-    # the token a new path ends in sits at its last position
-    tok = y_next.gather(0, (y_next_lens - 1).clamp(min=0).unsqueeze(0)).squeeze(0)
-    ctx.save_for_backward(next_src, tok, torch.isfinite(lp_next))
-    ctx.shape_t, ctx.dtype_t, ctx.dtype_prev = log_probs_t.shape, log_probs_t.dtype, log_probs_prev.dtype
-
-
-def _beam_search_advance_backward(ctx, g_y, g_lens, g_lp, g_src):
-    # log_probs_next[n, k] = log_probs_prev[n, src] + log_probs_t[n, src, tok] (reference
-    # _decoding.py:121-131: the top-k VALUES stay in the graph), so the gradient of an entry goes
-    # to exactly those two addends; padded (-inf) entries carry none
-    src, tok, valid = ctx.saved_tensors
-    N, Kp, V = ctx.shape_t
-    g = torch.where(valid, g_lp, torch.zeros_like(g_lp)).float()
-    g_prev = g.new_zeros((N, Kp)).scatter_add_(1, src, g)
-    g_t = g.new_zeros((N, Kp * V)).scatter_add_(1, src * V + tok.clamp(0, V - 1), g).view(N, Kp, V)
-    return g_t.to(ctx.dtype_t), None, g_prev.to(ctx.dtype_prev), None, None, None
-
-
-register_autograd(
-    "pydrobert_amd::beam_search_advance", _beam_search_advance_backward, setup_context=_beam_search_advance_setup
-)
-
-
-def beam_search_advance(
-    log_probs_t: torch.Tensor,
-    width: int,
-    log_probs_prev: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_lens: Optional[torch.Tensor] = None,
-) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Beam search step function (reference _decoding.py:41-155).
-
-    Returns ``(y_next, y_next_lens, log_probs_next, next_src)``.
-    """
-    if not torch.jit.is_scripting():
-        # nothing to trace, transform or differentiate: the implementation behind the operator, directly
-        if _cabi.plain_call(log_probs_t, log_probs_prev, y_prev, y_prev_lens):
-            return _beam_search_advance_impl(log_probs_t, width, log_probs_prev, y_prev, y_prev_lens)
-    return torch.ops.pydrobert_amd.beam_search_advance(
-        log_probs_t, width, log_probs_prev, y_prev, y_prev_lens
-    )
-
-
-def _ctc_prefix_search_advance_impl(
-    ext: torch.Tensor,
-    nonext: torch.Tensor,
-    blank: torch.Tensor,
-    width: int,
-    nb: torch.Tensor,
-    b: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_last: torch.Tensor,
-    y_prev_lens: torch.Tensor,
-    prev_is_prefix: torch.Tensor,
-    lm_mix: Optional[Tuple[float, bool]] = None,
-) -> Optional[Tuple[
-    torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
-    torch.Tensor, torch.Tensor,
-]]:  # fmt: skip
-    # `lm_mix` = (beta, valid_mixture): `ext` then holds the language model's scores (N, K', V) and the
-    # kernel mixes them with the frame's probabilities itself (pdt_ctc_prefix_search_advance_lm); None is
-    # returned when that entry point does not take the shapes (the caller makes the two calls)
-    if width < 1:
-        raise RuntimeError("width must be positive")
-    if ext.dim() != 3:
-        raise RuntimeError("ext_probs_t must be 3 dimensional")
-    N, Kp, V = ext.shape
-    if nonext.shape != (N, V):
-        raise RuntimeError(
-            "expected nonext_probs_t to have shape {}, got {}".format((N, V), tuple(nonext.shape))
-        )
-    if blank.shape != (N,):
-        raise RuntimeError(
-            "expected blank_probs_t to have shape {}, got {}".format((N,), tuple(blank.shape))
-        )
-    if nb.shape != (N, Kp):
-        raise RuntimeError(
-            "expected nb_probs_prev to have shape {}, got {}".format((N, Kp), tuple(nb.shape))
-        )
-    if b.shape != (N, Kp):
-        raise RuntimeError(
-            "expected b_probs_prev to have shape {}, got {}".format((N, Kp), tuple(b.shape))
-        )
-    if y_prev.dim() != 3:
-        raise RuntimeError("y_prev must be 3 dimensional")
-    if y_prev.shape[1:] != (N, Kp):
-        raise RuntimeError(
-            "expected last two dimensions of y_prev to be {}, got {}".format(
-                (N, Kp), tuple(y_prev.shape[1:])
-            )
-        )
-    S = y_prev.size(0)
-    if y_prev_last.shape != (N, Kp):
-        raise RuntimeError(
-            "expected y_prev_last to have shape {}, got {}".format((N, Kp), tuple(y_prev_last.shape))
-        )
-    if y_prev_lens.shape != (N, Kp):
-        raise RuntimeError(
-            "expected y_prev_lens to have shape {}, got {}".format((N, Kp), tuple(y_prev_lens.shape))
-        )
-    if prev_is_prefix.shape != (N, Kp, Kp):
-        raise RuntimeError(
-            "expected prev_is_prefix to have shape {}, got {}".format(
-                (N, Kp, Kp), tuple(prev_is_prefix.shape)
-            )
-        )
-    device = _cabi.require_hip(ext, nonext, blank, nb, b, y_prev, y_prev_last, y_prev_lens,
-                               prev_is_prefix)  # fmt: skip
-    dtype = ext.dtype if lm_mix is None else nonext.dtype
-    ext, nonext, blank, nb, b = (_f32(x) for x in (ext, nonext, blank, nb, b))
-    yp, last, lens = _i64(y_prev), _i64(y_prev_last), _i64(y_prev_lens)
-    isp = prev_is_prefix.detach() if prev_is_prefix.requires_grad else prev_is_prefix
-    if isp.dtype != torch.bool:
-        isp = isp.bool()
-    W = int(width)
-    with _cabi.on_device(device):
-        y_next = torch.empty((S + 1, N, W), device=device, dtype=torch.long)
-        o_last = torch.empty((N, W), device=device, dtype=torch.long)
-        o_lens = torch.empty((N, W), device=device, dtype=torch.long)
-        o_src = torch.empty((N, W), device=device, dtype=torch.long)
-        o_nb = torch.empty((N, W), device=device, dtype=torch.float)
-        o_b = torch.empty((N, W), device=device, dtype=torch.float)
-        o_isp = torch.empty((N, W, W), device=device, dtype=torch.bool)
-        o_non = torch.empty((N, W), device=device, dtype=torch.bool)
-        if N and lm_mix is not None:
-            ext = ext.contiguous()
-            rc = _cabi.lib().pdt_ctc_prefix_search_advance_lm(
-                _cabi.ptr(ext), float(lm_mix[0]), int(lm_mix[1]),
-                _cabi.ptr(nonext), nonext.stride(0), nonext.stride(1),
-                _cabi.ptr(blank), blank.stride(0), N, Kp, V, W,
-                _cabi.ptr(nb), nb.stride(0), nb.stride(1), _cabi.ptr(b), b.stride(0), b.stride(1),
-                _cabi.ptr(yp), S, yp.stride(0), yp.stride(1), yp.stride(2),
-                _cabi.ptr(last), last.stride(0), last.stride(1),
-                _cabi.ptr(lens), lens.stride(0), lens.stride(1),
-                _cabi.ptr(isp), isp.stride(0), isp.stride(1), isp.stride(2),
-                _cabi.ptr(y_next), _cabi.ptr(o_last), _cabi.ptr(o_lens), _cabi.ptr(o_nb),
-                _cabi.ptr(o_b), _cabi.ptr(o_isp), _cabi.ptr(o_src), _cabi.ptr(o_non),
-                _cabi.stream_ptr(device),
-            )  # fmt: skip
-            if rc == _cabi.PDT_E_UNSUPPORTED:
-                return None
-            _cabi.check(rc, "pdt_ctc_prefix_search_advance_lm")
-        elif N:
-            rc = _cabi.lib().pdt_ctc_prefix_search_advance(
-                _cabi.ptr(ext), ext.stride(0), ext.stride(1), ext.stride(2),
-                _cabi.ptr(nonext), nonext.stride(0), nonext.stride(1),
-                _cabi.ptr(blank), blank.stride(0), N, Kp, V, W,
-                _cabi.ptr(nb), nb.stride(0), nb.stride(1), _cabi.ptr(b), b.stride(0), b.stride(1),
-                _cabi.ptr(yp), S, yp.stride(0), yp.stride(1), yp.stride(2),
-                _cabi.ptr(last), last.stride(0), last.stride(1),
-                _cabi.ptr(lens), lens.stride(0), lens.stride(1),
-                _cabi.ptr(isp), isp.stride(0), isp.stride(1), isp.stride(2),
-                _cabi.ptr(y_next), _cabi.ptr(o_last), _cabi.ptr(o_lens), _cabi.ptr(o_nb),
-                _cabi.ptr(o_b), _cabi.ptr(o_isp), _cabi.ptr(o_src), _cabi.ptr(o_non),
-                _cabi.stream_ptr(device),
-            )  # fmt: skip
-            _cabi.check(rc, "pdt_ctc_prefix_search_advance")
-    if dtype != torch.float:
-        o_nb, o_b = o_nb.to(dtype), o_b.to(dtype)
-    return y_next, o_last, o_lens, o_nb, o_b, o_isp, o_src, o_non
-
-
-@custom_op("pydrobert_amd::ctc_prefix_search_advance", mutates_args=())
-def _ctc_prefix_search_advance_op(
-    ext: torch.Tensor,
-    nonext: torch.Tensor,
-    blank: torch.Tensor,
-    width: int,
-    nb: torch.Tensor,
-    b: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_last: torch.Tensor,
-    y_prev_lens: torch.Tensor,
-    prev_is_prefix: torch.Tensor,
-) -> Tuple[
-    torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
-    torch.Tensor, torch.Tensor,
-]:  # fmt: skip
-    return _ctc_prefix_search_advance_impl(
-        ext, nonext, blank, width, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix
-    )
-
-
-def _ctc_prefix_search_advance_lm_impl(
-    lm_log_probs: torch.Tensor,
-    beta: float,
-    valid_mixture: bool,
-    nonext: torch.Tensor,
-    blank: torch.Tensor,
-    width: int,
-    nb: torch.Tensor,
-    b: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_last: torch.Tensor,
-    y_prev_lens: torch.Tensor,
-    prev_is_prefix: torch.Tensor,
-) -> Tuple[
-    torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
-    torch.Tensor, torch.Tensor,
-]:  # fmt: skip
-    """``fusion_ext`` + ``ctc_prefix_search_advance`` as ONE kernel: the extension probabilities (reference
-    _decoding.py:1110-1135) are formed inside the step and never written.  ``lm_log_probs`` is ``(N, K', V)``.
-    No gradient; shapes the kernel does not take (V > 1024, beams above 32) make the two calls here."""
-    out = _ctc_prefix_search_advance_impl(
-        lm_log_probs, nonext, blank, width, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix,
-        (beta, valid_mixture),
-    )  # fmt: skip
-    if out is None:
-        N, Kp, V = lm_log_probs.shape
-        ext = _fusion_ext_impl(lm_log_probs.reshape(N * Kp, V), nonext, blank, beta, valid_mixture)
-        out = _ctc_prefix_search_advance_impl(
-            ext, nonext, blank, width, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix
-        )
-    return out
-
-
-@custom_op("pydrobert_amd::ctc_prefix_search_advance_lm", mutates_args=())
-def _ctc_prefix_search_advance_lm_op(
-    lm_log_probs: torch.Tensor,
-    beta: float,
-    valid_mixture: bool,
-    nonext: torch.Tensor,
-    blank: torch.Tensor,
-    width: int,
-    nb: torch.Tensor,
-    b: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_last: torch.Tensor,
-    y_prev_lens: torch.Tensor,
-    prev_is_prefix: torch.Tensor,
-) -> Tuple[
-    torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
-    torch.Tensor, torch.Tensor,
-]:  # fmt: skip
-    return _ctc_prefix_search_advance_lm_impl(
-        lm_log_probs, beta, valid_mixture, nonext, blank, width, nb, b, y_prev, y_prev_last, y_prev_lens,
-        prev_is_prefix,
-    )  # fmt: skip
-
-
-@_ctc_prefix_search_advance_lm_op.register_fake
-def _(lm_log_probs, beta, valid_mixture, nonext, blank, width, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix):
-    N, W, S = lm_log_probs.shape[0], width, y_prev.shape[0]
-    i64 = lambda *s: y_prev.new_empty(s, dtype=torch.long)  # noqa: E731
-    return (
-        i64(S + 1, N, W), i64(N, W), i64(N, W), nonext.new_empty((N, W)), nonext.new_empty((N, W)),
-        nonext.new_empty((N, W, W), dtype=torch.bool), i64(N, W), nonext.new_empty((N, W), dtype=torch.bool),
-    )  # fmt: skip
-
-
-def _ctc_step_with_lm_scores(lm_log_probs, beta, valid_mixture, nonext, blank, width, nb, b, y_prev, y_prev_last,
-                             y_prev_lens, prev_is_prefix):
-    """The operator above, or -- nothing tracing, transforming or differentiating -- what is behind it."""
-    args = (lm_log_probs, beta, valid_mixture, nonext, blank, width, nb, b, y_prev, y_prev_last, y_prev_lens,
-            prev_is_prefix)  # fmt: skip
-    if _cabi.plain_call(lm_log_probs, nonext, blank, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix):
-        return _ctc_prefix_search_advance_lm_impl(*args)
-    return torch.ops.pydrobert_amd.ctc_prefix_search_advance_lm(*args)
-
-
-@_ctc_prefix_search_advance_op.register_fake
-def _(ext, nonext, blank, width, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix):
-    N, W, S = ext.shape[0], width, y_prev.shape[0]
-    i64 = lambda *s: y_prev.new_empty(s, dtype=torch.long)  # noqa: E731
-    return (
-        i64(S + 1, N, W), i64(N, W), i64(N, W), ext.new_empty((N, W)), ext.new_empty((N, W)),
-        ext.new_empty((N, W, W), dtype=torch.bool), i64(N, W), ext.new_empty((N, W), dtype=torch.bool),
-    )  # fmt: skip
-
-
-def _ctc_advance_setup(ctx, inputs, output):
-    ext, nonext, blank, _, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix = inputs
-    _, o_last, _, o_nb, _, _, o_src, o_non = output
-    ctx.save_for_backward(ext, nonext, blank, nb, b, y_prev, y_prev_last, y_prev_lens, prev_is_prefix,
-                          o_last, o_nb, o_src, o_non)  # fmt: skip
-
-
-def _ctc_advance_backward(ctx, g_y, g_last, g_lens, g_nb, g_b, g_isp, g_src, g_non):
-    """Adjoint of the masses of one CTC prefix-search step (reference _decoding.py:777-880; the
-    selection itself is piecewise constant).  A new entry i with source s = next_src[i] holds
-      extension by v:   nb' = w(s, v) * ext[s, v],  b' = 0,   w(s, v) = (nb[s] if v != last[s] else 0) + b[s]
-      non-extension:    nb' = nb[s] * nonext[last[s]] + sum over prefixes k that BECOME s when extended
-                              by need(k, s) of w(k, need) * ext[k, need],
-                        b'  = (nb[s] + b[s]) * blank
-    The dense work is (N, K', K') -- nothing of size V besides the scatter into grad ext."""
-    (ext, nonext, blank, nb, b, y_prev, last, lens, is_prefix, o_last, o_nb, src, non) = ctx.saved_tensors
-    N, Kp, V = ext.shape
-    S = y_prev.shape[0]
-    f = torch.float
-    ext_, nonext_, blank_, nb_, b_ = ext.to(f), nonext.to(f), blank.to(f), nb.to(f), b.to(f)
-    valid = torch.isfinite(o_nb)
-    zero = torch.zeros((), device=ext.device, dtype=f)
-    # absent (padded) prefixes hold -inf masses: they are the source of nothing valid
-    nb_, b_ = torch.where(torch.isfinite(nb_), nb_, zero), torch.where(torch.isfinite(b_), b_, zero)
-    gnb = torch.where(valid, g_nb.to(f), zero)
-    gb = torch.where(valid & non, g_b.to(f), zero)
-    lastc = last.clamp(0, V - 1)
-    # --- extension entries
-    is_ext = valid & ~non
-    tok = o_last.clamp(0, V - 1)
-    last_s = lastc.gather(1, src)
-    w = torch.where(tok != last_s, nb_.gather(1, src), zero) + b_.gather(1, src)
-    e = ext_.reshape(N, Kp * V).gather(1, src * V + tok)
-    ge = torch.where(is_ext, gnb, zero)
-    g_ext = ge.new_zeros((N, Kp * V)).scatter_add_(1, src * V + tok, ge * w)
-    g_nb_prev = ge.new_zeros((N, Kp)).scatter_add_(1, src, torch.where(tok != last_s, ge * e, zero))
-    g_b_prev = ge.new_zeros((N, Kp)).scatter_add_(1, src, ge * e)
-    # --- non-extension entries: gradient of stay_nb[s] / stay_b[s], summed over the entries that kept s
-    gs_nb = ge.new_zeros((N, Kp)).scatter_add_(1, src, torch.where(non, gnb, zero))
-    gs_b = ge.new_zeros((N, Kp)).scatter_add_(1, src, gb)
-    p_last = nonext_.gather(1, lastc)
-    g_nonext = ge.new_zeros((N, V)).scatter_add_(1, lastc, gs_nb * nb_)
-    g_nb_prev = g_nb_prev + gs_nb * p_last + gs_b * blank_.unsqueeze(1)
-    g_b_prev = g_b_prev + gs_b * blank_.unsqueeze(1)
-    g_blank = (gs_b * (nb_ + b_)).sum(1)
-    # merged extensions: prefix k + need(k, s) == prefix s
-    if S:
-        at = lens.clamp(max=S - 1).unsqueeze(2).expand(N, Kp, Kp).transpose(0, 1)
-        need = y_prev.gather(0, at).transpose(0, 1).clamp(0, V - 1)  # (N, k, s)
-    else:
-        need = torch.zeros((N, Kp, Kp), dtype=torch.long, device=ext.device)
-    becomes = ((lens + 1).unsqueeze(2) == lens.unsqueeze(1)) & is_prefix.bool()
-    gm = torch.where(becomes, gs_nb.unsqueeze(1).expand(N, Kp, Kp), zero)  # d stay_nb[s] / d term(k, s)
-    differs = need != lastc.unsqueeze(2)
-    wk = torch.where(differs, nb_.unsqueeze(2), zero) + b_.unsqueeze(2)
-    ek = ext_.gather(2, need)
-    k_idx = torch.arange(Kp, device=ext.device).view(1, Kp, 1)
-    g_ext.scatter_add_(1, (k_idx * V + need).reshape(N, Kp * Kp), (gm * wk).reshape(N, Kp * Kp))
-    g_nb_prev = g_nb_prev + torch.where(differs, gm * ek, zero).sum(2)
-    g_b_prev = g_b_prev + (gm * ek).sum(2)
-    return (g_ext.view(N, Kp, V).to(ext.dtype), g_nonext.to(nonext.dtype), g_blank.to(blank.dtype), None,
-            g_nb_prev.to(nb.dtype), g_b_prev.to(b.dtype), None, None, None, None)  # fmt: skip
-
-
-register_autograd(
-    "pydrobert_amd::ctc_prefix_search_advance", _ctc_advance_backward, setup_context=_ctc_advance_setup
-)
-
-
-def ctc_prefix_search_advance(
-    probs_t: Tuple[torch.Tensor, torch.Tensor, torch.Tensor],
-    width: int,
-    probs_prev: Tuple[torch.Tensor, torch.Tensor],
-    y_prev: torch.Tensor,
-    y_prev_last: torch.Tensor,
-    y_prev_lens: torch.Tensor,
-    prev_is_prefix: torch.Tensor,
-) -> Tuple[
-    torch.Tensor, torch.Tensor, torch.Tensor, Tuple[torch.Tensor, torch.Tensor], torch.Tensor,
-    torch.Tensor, torch.Tensor,
-]:  # fmt: skip
-    """CTC prefix search step function (reference _decoding.py:636-934).
-
-    Returns ``(y_next, y_next_last, y_next_lens, (nb_probs_next, b_probs_next),
-    next_is_prefix, next_src, next_is_nonext)``.
-    """
-    if not torch.jit.is_scripting():
-        # nothing to trace, transform or differentiate: the implementation behind the operator, directly
-        if _cabi.plain_call(probs_t[0], probs_t[1], probs_t[2], probs_prev[0], probs_prev[1], y_prev,
-                            y_prev_last, y_prev_lens, prev_is_prefix):  # fmt: skip
-            y_next, last, lens, nb, b, isp, src, non = _ctc_prefix_search_advance_impl(
-                probs_t[0], probs_t[1], probs_t[2], width, probs_prev[0], probs_prev[1], y_prev,
-                y_prev_last, y_prev_lens, prev_is_prefix,
-            )  # fmt: skip
-            return y_next, last, lens, (nb, b), isp, src, non
-    y_next, last, lens, nb, b, isp, src, non = torch.ops.pydrobert_amd.ctc_prefix_search_advance(
-        probs_t[0], probs_t[1], probs_t[2], width, probs_prev[0], probs_prev[1], y_prev,
-        y_prev_last, y_prev_lens, prev_is_prefix,
-    )  # fmt: skip
-    return y_next, last, lens, (nb, b), isp, src, non
 
 
 @custom_op("pydrobert_amd::ctc_prefix_search", mutates_args=())
@@ -597,43 +96,6 @@ def ctc_prefix_search(
     ):
         return torch.ops.pydrobert_amd.ctc_prefix_search(logits, width, lens)
     return CTCPrefixSearch(width)(logits, lens)
-
-
-def _fusion_ext_impl(
-    lm_log_probs: torch.Tensor, nonext: torch.Tensor, blank: torch.Tensor, beta: float, valid_mixture: bool
-) -> torch.Tensor:
-    """Extension probabilities ``(N, K', V)`` of one frame from the LM scores ``(N * K', V)`` and
-    the frame's CTC probabilities, in one pass (``csrc/fusion_ext.hip``; reference
-    _decoding.py:1110-1135).  No gradient: ``CTCPrefixSearch`` composes torch ops instead when
-    one is wanted."""
-    N, V = nonext.shape
-    if lm_log_probs.dim() != 2 or lm_log_probs.size(1) != V or (N and lm_log_probs.size(0) % N):
-        raise RuntimeError("lm_log_probs must be of shape (N * K', V)")
-    Kp = lm_log_probs.size(0) // N if N else 1
-    device = _cabi.require_hip(lm_log_probs, nonext, blank)
-    lm, ne, bl = _f32(lm_log_probs).contiguous(), _f32(nonext), _f32(blank)
-    with _cabi.on_device(device):
-        out = torch.empty((N, Kp, V), device=device, dtype=torch.float)
-        if N and V:
-            rc = _cabi.lib().pdt_fusion_ext(
-                _cabi.ptr(lm), N, Kp, V, _cabi.ptr(ne), ne.stride(0), ne.stride(1), _cabi.ptr(bl),
-                bl.stride(0), float(beta), int(valid_mixture), _cabi.ptr(out), _cabi.stream_ptr(device),
-            )  # fmt: skip
-            _cabi.check(rc, "pdt_fusion_ext")
-    return out.to(nonext.dtype)
-
-
-@custom_op("pydrobert_amd::fusion_ext", mutates_args=())
-def _fusion_ext_op(
-    lm_log_probs: torch.Tensor, nonext: torch.Tensor, blank: torch.Tensor, beta: float, valid_mixture: bool
-) -> torch.Tensor:
-    return _fusion_ext_impl(lm_log_probs, nonext, blank, beta, valid_mixture)
-
-
-@_fusion_ext_op.register_fake
-def _(lm_log_probs, nonext, blank, beta, valid_mixture):
-    N, V = nonext.shape
-    return nonext.new_empty((N, lm_log_probs.shape[0] // max(N, 1), V))
 
 
 class CTCPrefixSearch(torch.nn.Module):
@@ -1338,695 +800,3 @@ class BeamSearch(torch.nn.Module):
         if batch_size is None:
             y, lens, log_probs = y.squeeze(1), lens.squeeze(0), log_probs.squeeze(0)
         return y, lens, log_probs
-
-
-# ---------------------------------------------------------------------------------------
-# greedy CTC search, sequence log-probabilities, random walk
-# ---------------------------------------------------------------------------------------
-@custom_op("pydrobert_amd::ctc_greedy_search", mutates_args=())
-def _ctc_greedy_search_op(
-    logits: torch.Tensor,
-    in_lens: Optional[torch.Tensor],
-    blank_idx: int,
-    batch_first: bool,
-    is_probs: bool,
-) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    if logits.dim() != 3:
-        raise RuntimeError("logits must be 3-dimensional")
-    V = logits.size(2)
-    if blank_idx < -V or blank_idx > (V - 1):
-        raise RuntimeError(
-            "Blank index out of range (expected to be in the range of [-{},{}], but got {})".format(
-                V, V - 1, blank_idx
-            )
-        )
-    blank_idx = (blank_idx + V) % V
-    device = _cabi.require_hip(logits, in_lens)
-    x = _f32(logits)
-    if batch_first:
-        N, T = x.shape[:2]
-        st, sn = x.stride(1), x.stride(0)
-    else:
-        T, N = x.shape[:2]
-        st, sn = x.stride(0), x.stride(1)
-    lens = None if in_lens is None else _i64(in_lens).contiguous()
-    with torch.cuda.device(device):
-        max_ = torch.empty((N,), device=device, dtype=torch.float)
-        paths = torch.empty((N, T) if batch_first else (T, N), device=device, dtype=torch.long)
-        out_lens = torch.empty((N,), device=device, dtype=torch.long)
-        pst, psn = (paths.stride(1), paths.stride(0)) if batch_first else (paths.stride(0), paths.stride(1))
-        rc = _cabi.lib().pdt_ctc_greedy_search(
-            _cabi.ptr(x), T, N, V, st, sn, x.stride(2), _cabi.ptr(lens), blank_idx, int(is_probs),
-            _cabi.ptr(max_), _cabi.ptr(paths), pst, psn, _cabi.ptr(out_lens), _cabi.stream_ptr(device),
-        )  # fmt: skip
-    _cabi.check(rc, "pdt_ctc_greedy_search")
-    return max_.to(logits.dtype), paths, out_lens
-
-
-@_ctc_greedy_search_op.register_fake
-def _(logits, in_lens, blank_idx, batch_first, is_probs):
-    N = logits.shape[0] if batch_first else logits.shape[1]
-    return (
-        logits.new_empty((N,)),
-        logits.new_empty(logits.shape[:2], dtype=torch.long),
-        logits.new_empty((N,), dtype=torch.long),
-    )
-
-
-def _ctc_greedy_setup(ctx, inputs, output):
-    logits, in_lens, _, batch_first, is_probs = inputs
-    ctx.save_for_backward(logits, in_lens)
-    ctx.cfg = (batch_first, is_probs)
-
-
-def _ctc_greedy_backward(ctx, g_max, g_paths, g_lens):
-    """``max_`` is the sum (product) over the valid frames of the best class's log-probability
-    (probability): differentiable in the reference (_decoding.py:526-553).  The frames' maxima
-    are recomputed with device ops and differentiated by autograd."""
-    logits, in_lens = ctx.saved_tensors
-    batch_first, is_probs = ctx.cfg
-    with torch.enable_grad():
-        x = logits.detach().requires_grad_(True)
-        y = x if is_probs else x.log_softmax(2)
-        if not batch_first:
-            y = y.transpose(0, 1)
-        best = y.max(2)[0]  # (N, T)
-        if in_lens is not None:
-            valid = torch.arange(best.size(1), device=best.device).unsqueeze(0) < in_lens.unsqueeze(1)
-            best = best.masked_fill(~valid, 1.0 if is_probs else 0.0)
-        total = best.prod(1) if is_probs else best.sum(1)
-        (g,) = torch.autograd.grad(total, x, g_max.to(total.dtype))
-    return g, None, None, None, None
-
-
-register_autograd("pydrobert_amd::ctc_greedy_search", _ctc_greedy_backward, setup_context=_ctc_greedy_setup)
-
-
-def ctc_greedy_search(
-    logits: torch.Tensor,
-    in_lens: Optional[torch.Tensor] = None,
-    blank_idx: int = -1,
-    batch_first: bool = False,
-    is_probs: bool = False,
-) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-    """Functional version of :class:`CTCGreedySearch` (reference _decoding.py:507-558):
-    returns ``(max_, paths, out_lens)``.  One pass over the logits."""
-    return torch.ops.pydrobert_amd.ctc_greedy_search(logits, in_lens, blank_idx, batch_first, is_probs)
-
-
-def _slp_dims(hyp: torch.Tensor, dim: int) -> Tuple[int, int, int, int]:
-    hyp_dim = hyp.dim()
-    if dim < -hyp_dim or dim > hyp_dim - 1:
-        raise RuntimeError(
-            "Dimension out of range (expected to be in range of [{}, {}], but got {})".format(
-                -hyp_dim, hyp_dim - 1, dim
-            )
-        )
-    dim = (hyp_dim + dim) % hyp_dim
-    shape = tuple(hyp.shape)
-    return dim, int(math.prod(shape[:dim])), shape[dim], int(math.prod(shape[dim + 1 :]))
-
-
-@custom_op("pydrobert_amd::sequence_log_probs", mutates_args=())
-def _sequence_log_probs_op(
-    logits: torch.Tensor, hyp: torch.Tensor, dim: int, eos: Optional[int]
-) -> torch.Tensor:
-    """Fused log-softmax + gather + masked sum over ``dim`` (csrc/seq_ops.hip)."""
-    dim, A, S, B = _slp_dims(hyp, dim)
-    if logits.shape[:-1] != hyp.shape:
-        raise RuntimeError("logits must have shape hyp.shape + (num_classes,)")
-    device = _cabi.require_hip(logits, hyp)
-    x = _f32(logits).contiguous()
-    h = _i64(hyp).contiguous()
-    with torch.cuda.device(device):
-        out = torch.empty((A, B), device=device, dtype=torch.float)
-        rc = _cabi.lib().pdt_sequence_log_probs_forward(
-            _cabi.ptr(x), _cabi.ptr(h), A, S, B, x.shape[-1], int(eos is not None),
-            int(eos) if eos is not None else 0, _cabi.ptr(out), _cabi.stream_ptr(device),
-        )  # fmt: skip
-    _cabi.check(rc, "pdt_sequence_log_probs_forward")
-    shape = tuple(hyp.shape)
-    return out.view(shape[:dim] + shape[dim + 1 :]).to(logits.dtype)
-
-
-@_sequence_log_probs_op.register_fake
-def _(logits, hyp, dim, eos):
-    d = dim % hyp.dim()
-    return logits.new_empty(tuple(hyp.shape[:d]) + tuple(hyp.shape[d + 1 :]))
-
-
-@custom_op("pydrobert_amd::sequence_log_probs_backward", mutates_args=())
-def _sequence_log_probs_backward_op(
-    logits: torch.Tensor, hyp: torch.Tensor, dim: int, eos: Optional[int], grad_out: torch.Tensor
-) -> torch.Tensor:
-    dim, A, S, B = _slp_dims(hyp, dim)
-    device = logits.device
-    x = _f32(logits).contiguous()
-    h = _i64(hyp).contiguous()
-    g = grad_out.detach().float().contiguous()
-    with torch.cuda.device(device):
-        grad = torch.empty_like(x)
-        rc = _cabi.lib().pdt_sequence_log_probs_backward(
-            _cabi.ptr(x), _cabi.ptr(h), A, S, B, x.shape[-1], int(eos is not None),
-            int(eos) if eos is not None else 0, _cabi.ptr(g), _cabi.ptr(grad),
-            _cabi.stream_ptr(device),
-        )  # fmt: skip
-    _cabi.check(rc, "pdt_sequence_log_probs_backward")
-    return grad.view(logits.shape).to(logits.dtype)
-
-
-@_sequence_log_probs_backward_op.register_fake
-def _(logits, hyp, dim, eos, grad_out):
-    return torch.empty_like(logits)
-
-
-def _slp_setup_context(ctx, inputs, output):
-    logits, hyp, dim, eos = inputs
-    ctx.save_for_backward(logits, hyp)
-    ctx.cfg = (dim, eos)
-
-
-def _slp_backward(ctx, grad_out):
-    logits, hyp = ctx.saved_tensors
-    dim, eos = ctx.cfg
-    grad = torch.ops.pydrobert_amd.sequence_log_probs_backward(logits, hyp, dim, eos, grad_out)
-    return grad, None, None, None
-
-
-register_autograd(
-    "pydrobert_amd::sequence_log_probs", _slp_backward, setup_context=_slp_setup_context
-)
-
-
-def _sequence_log_probs_ps(
-    logits: Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]],
-    hyp: torch.Tensor,
-    dim: int,
-) -> torch.Tensor:
-    # padded view + out-of-range tokens beyond each length: same kernel, same masking rule
-    if dim < -2 or dim > 1:
-        raise RuntimeError(
-            "Dimension out of range (expected to be in range of [-2, 1], but got {})".format(dim)
-        )
-    data, batch_sizes, unsorted = logits[0], logits[1], logits[3]
-    S = batch_sizes.size(0)
-    padded, lens = torch._pad_packed_sequence(data, batch_sizes, False, 0.0, S)  # (S, N, V)
-    if unsorted is not None:
-        padded, lens = padded.index_select(1, unsorted), lens.index_select(0, unsorted.cpu())
-    h = hyp if dim % 2 == 0 else hyp.t()
-    h = h[:S]
-    beyond = torch.arange(S, device=h.device).unsqueeze(1) >= lens.to(h.device).unsqueeze(0)
-    return torch.ops.pydrobert_amd.sequence_log_probs(padded, h.masked_fill(beyond, -1), 0, None)
-
-
-def sequence_log_probs(
-    logits: Any, hyp: torch.Tensor, dim: int = 0, eos: Optional[int] = None
-) -> torch.Tensor:
-    """Functional version of :class:`SequenceLogProbabilities` (reference
-    _decoding.py:1516-1633): joint log-probability of the token sequences ``hyp`` under
-    ``logits`` (a tensor of shape ``hyp.shape + (V,)`` or a ``PackedSequence``).  Fused
-    log-softmax + gather + masked sum; differentiable w.r.t. ``logits``."""
-    if isinstance(logits, torch.Tensor):
-        return torch.ops.pydrobert_amd.sequence_log_probs(logits, hyp, dim, eos)
-    elif torch.jit.isinstance(
-        logits, Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor], Optional[torch.Tensor]]
-    ):
-        return _sequence_log_probs_ps(logits, hyp, dim)
-    raise RuntimeError("logits must be either a Tensor or PackedSequence")
-
-
-_WALK_INVALID, _WALK_REACH, _WALK_BAD_LENS = 2, 4, 8
-
-
-def _walk_launch(device: torch.device, launch, what: str) -> Tuple[int, int, int]:
-    """``launch(host_report_ptr)`` enqueues one random-walk kernel; returns its report ``(bits, live,
-    longest)`` once it is done (include/pdt_amd.h, "Random walks": word 0 = PDT_WALK_DONE | bits, stored
-    last; one wait on it in pinned host memory, no device-to-host copy).  A row the kernel could draw
-    nothing from raises (the reference's sampler would hit a device assert)."""
-    report = _cabi.host_report(device)
-    rc = launch(report.ptr)
-    if rc:
-        report.disarm()
-        _cabi.check(rc, what)
-    bits = report.wait()
-    if bits & _WALK_INVALID:
-        raise RuntimeError(
-            "{}: a row of log-probabilities has no positive finite mass (every entry -inf, a NaN or +inf); "
-            "nothing can be sampled from it".format(what)
-        )
-    return bits, report.read(1), report.read(2)
-
-
-def _random_walk_checks(
-    log_probs_t: torch.Tensor,
-    log_probs_prev: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_lens: Optional[torch.Tensor],
-) -> None:
-    if log_probs_t.dim() != 2:
-        raise RuntimeError("log_probs_t must be 2-dimensional")
-    N = log_probs_t.size(0)
-    if log_probs_prev.dim() != 1 or log_probs_prev.size(0) != N:
-        raise RuntimeError(
-            "Expected log_probs_prev to be of shape ({},), got {}".format(N, log_probs_prev.shape)
-        )
-    if y_prev.dim() != 2:
-        raise RuntimeError("y_prev must be 2-dimensional")
-    if y_prev.size(1) != N:
-        raise RuntimeError("Expected dim 1 of y_prev to be {}, got {}".format(N, y_prev.size(-1)))
-    if y_prev_lens is not None and (y_prev_lens.dim() != 1 or y_prev_lens.size(0) != N):
-        raise RuntimeError(
-            "Expected y_prev_lens to have shape ({},), got {}".format(N, y_prev_lens.shape)
-        )
-
-
-@custom_op("pydrobert_amd::random_walk_advance", mutates_args=())
-def _random_walk_advance_op(
-    log_probs_t: torch.Tensor,
-    u: torch.Tensor,
-    log_probs_prev: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_lens: Optional[torch.Tensor],
-) -> Tuple[torch.Tensor, torch.Tensor]:
-    """random_walk_advance with the uniforms given: token n is drawn from row n of ``log_probs_t`` by the
-    rule of include/pdt_amd.h with ``u[n]``; one kernel (csrc/random_walk.hip), one host wait."""
-    _random_walk_checks(log_probs_t, log_probs_prev, y_prev, y_prev_lens)
-    N, V = log_probs_t.shape
-    if u.shape != (N,):
-        raise RuntimeError("Expected u to be of shape ({},), got {}".format(N, tuple(u.shape)))
-    device = _cabi.require_hip(log_probs_t, u, log_probs_prev, y_prev, y_prev_lens)
-    lpt, uu, lpp, yp = _f32(log_probs_t), _f32(u), _f32(log_probs_prev), _i64(y_prev)
-    ypl = None if y_prev_lens is None else _i64(y_prev_lens)
-    S = yp.size(0)
-    grow = True
-    with _cabi.on_device(device):
-        y_next = torch.empty((S + 1, N), device=device, dtype=torch.long)
-        lp_next = torch.empty((N,), device=device, dtype=torch.float)
-        if N:
-            ctl = torch.zeros((4,), device=device, dtype=torch.int32)
-            bits, _, _ = _walk_launch(
-                device,
-                lambda host: _cabi.lib().pdt_random_walk_advance(
-                    _cabi.ptr(lpt), lpt.stride(0), lpt.stride(1), N, V, _cabi.ptr(uu), uu.stride(0),
-                    _cabi.ptr(lpp), lpp.stride(0), _cabi.ptr(yp), S, yp.stride(0), yp.stride(1),
-                    _cabi.ptr(ypl), 0 if ypl is None else ypl.stride(0), _cabi.ptr(y_next), _cabi.ptr(lp_next),
-                    _cabi.ptr(ctl), host, _cabi.stream_ptr(device),
-                ),
-                "random_walk_advance",
-            )  # fmt: skip
-            if bits & _WALK_BAD_LENS:
-                raise RuntimeError("random_walk_advance: y_prev_lens must lie in [0, {}]".format(S))
-            # :1272-1276 don't make y bigger unless some path reaches the end of the history
-            grow = ypl is None or S == 0 or bool(bits & _WALK_REACH)
-    if not grow:
-        y_next = y_next[:S]
-    return y_next, lp_next.to(torch.promote_types(log_probs_prev.dtype, log_probs_t.dtype))
-
-
-@_random_walk_advance_op.register_fake
-def _(log_probs_t, u, log_probs_prev, y_prev, y_prev_lens):
-    N, S = log_probs_t.shape[0], y_prev.shape[0]
-    if y_prev_lens is None or S == 0:
-        S_out = S + 1
-    else:  # data dependent: S or S + 1 (:1272-1276)
-        S_out = torch.library.get_ctx().new_dynamic_size()
-    return (
-        log_probs_t.new_empty((S_out, N), dtype=torch.long),
-        log_probs_t.new_empty((N,), dtype=torch.promote_types(log_probs_prev.dtype, log_probs_t.dtype)),
-    )
-
-
-def _rwa_setup_context(ctx, inputs, output):
-    log_probs_t, _, log_probs_prev, y_prev, y_prev_lens = inputs
-    y_next = output[0]
-    S = y_prev.size(0)
-    if S == 0 or y_prev_lens is None or y_next.size(0) > S:
-        tok = y_next[S]  # (the row the reference appends holds every walk's token)
-    else:
-        tok = y_next.gather(0, y_prev_lens.long().unsqueeze(0)).squeeze(0)
-    ctx.save_for_backward(tok)
-    ctx.cfg = (tuple(log_probs_t.shape), log_probs_t.dtype, log_probs_prev.dtype)
-
-
-def _rwa_backward(ctx, g_y, g_lp):
-    """``log_probs_next = log_probs_prev + log_probs_t[n, token]``: the gradient is ``g`` at the drawn token
-    of each row and ``g`` itself for ``log_probs_prev`` (the reference's gather, :1268)."""
-    (tok,) = ctx.saved_tensors
-    shape, lpt_dtype, lpp_dtype = ctx.cfg
-    if g_lp is None:
-        return None, None, None, None, None
-    g_lpt = torch.zeros(shape, dtype=lpt_dtype, device=tok.device)
-    g_lpt.scatter_(1, tok.unsqueeze(1), g_lp.unsqueeze(1).to(lpt_dtype))
-    return g_lpt, None, g_lp.to(lpp_dtype), None, None
-
-
-register_autograd("pydrobert_amd::random_walk_advance", _rwa_backward, setup_context=_rwa_setup_context)
-
-
-@custom_op("pydrobert_amd::random_walk_step", mutates_args=("y", "lens", "ended", "log_probs", "ctl"))
-def _random_walk_step_op(
-    scores: torch.Tensor,
-    u: torch.Tensor,
-    y: torch.Tensor,
-    t: int,
-    lens: torch.Tensor,
-    ended: torch.Tensor,
-    log_probs: torch.Tensor,
-    ctl: torch.Tensor,
-    eos: Optional[int],
-) -> int:
-    """One iteration of RandomWalk.forward with the default hook (csrc/random_walk.hip): from the model's
-    ``scores (N, V)`` and ``u (N,)``, row ``t`` of ``y (T, N)`` and the walks' ``lens`` / ``ended`` /
-    ``log_probs`` in place.  ``ctl``: four int32 on the device, zero.  Returns how many walks have not
-    ended (all of them when ``eos`` is None)."""
-    if scores.dim() != 2:
-        raise RuntimeError("scores must be 2-dimensional")
-    N, V = scores.shape
-    if y.dim() != 2 or y.size(1) != N or not 0 <= t < y.size(0):
-        raise RuntimeError("random_walk_step: y must be (T, {}) with T > t = {}".format(N, t))
-    for name, x, dt in (("u", u, torch.float), ("lens", lens, torch.long), ("ended", ended, torch.bool),
-                        ("log_probs", log_probs, torch.float)):  # fmt: skip
-        if x.shape != (N,) or x.dtype != dt or not x.is_contiguous():
-            raise RuntimeError("random_walk_step: {} must be a contiguous {} tensor of shape ({},)".format(name, dt, N))
-    if y.dtype != torch.long or not y.is_contiguous() or ctl.dtype != torch.int32 or ctl.numel() < 4:
-        raise RuntimeError("random_walk_step: y must be contiguous int64, ctl four int32")
-    device = _cabi.require_hip(scores, u, y, lens, ended, log_probs, ctl)
-    x = _f32(scores)
-    if N == 0:
-        return 0
-    _, live, _ = _walk_launch(
-        device,
-        lambda host: _cabi.lib().pdt_random_walk_step(
-            _cabi.ptr(x), x.stride(0), x.stride(1), N, V, _cabi.ptr(u), int(eos is not None), int(eos or 0),
-            y.data_ptr() + 8 * t * N, _cabi.ptr(lens), _cabi.ptr(ended), _cabi.ptr(log_probs), _cabi.ptr(ctl),
-            host, _cabi.stream_ptr(device),
-        ),
-        "random_walk_step",
-    )  # fmt: skip
-    return live
-
-
-@_random_walk_step_op.register_fake
-def _(scores, u, y, t, lens, ended, log_probs, ctl, eos):
-    return scores.shape[0]
-
-
-def random_walk_advance(
-    log_probs_t: torch.Tensor,
-    log_probs_prev: torch.Tensor,
-    y_prev: torch.Tensor,
-    y_prev_lens: Optional[torch.Tensor] = None,
-) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Random walk step function (reference _decoding.py:1207-1283).  On the GPU: one uniform per row from
-    torch's generator on the device, then ONE kernel draws every token (the rule of include/pdt_amd.h),
-    forms the log-probabilities and the next history; differentiable with respect to ``log_probs_t`` and
-    ``log_probs_prev``.  CPU tensors take the reference's torch body."""
-    _random_walk_checks(log_probs_t, log_probs_prev, y_prev, y_prev_lens)
-    if log_probs_t.device.type == "cuda":
-        u = torch.rand((log_probs_t.size(0),), device=log_probs_t.device, dtype=torch.float)
-        return torch.ops.pydrobert_amd.random_walk_advance(log_probs_t, u, log_probs_prev, y_prev, y_prev_lens)
-    S = y_prev.size(0)
-    y_t = torch.multinomial(log_probs_t.exp(), 1, True)  # (N, 1)
-    log_probs_next = log_probs_prev + log_probs_t.gather(1, y_t).squeeze(1)
-    y_t = y_t.T
-    if S:
-        if y_prev_lens is None:
-            y_next = torch.cat([y_prev, y_t], 0)
-        else:
-            y_next = torch.cat([y_prev, y_t], 0) if int(y_prev_lens.max().item()) >= S else y_prev
-            y_next = y_next.scatter(0, y_prev_lens.unsqueeze(0), y_t)
-    else:
-        y_next = y_t
-    return y_next, log_probs_next
-
-
-class CTCGreedySearch(torch.nn.Module):
-    """CTC greedy search (reference _decoding.py:561-635)."""
-
-    __constants__ = "blank_idx", "batch_first", "is_probs"
-
-    def __init__(self, blank_idx: int = -1, batch_first: bool = False, is_probs: bool = False):
-        blank_idx = argcheck.is_int(blank_idx, "blank_idx")
-        batch_first = argcheck.is_bool(batch_first, "batch_first")
-        is_probs = argcheck.is_bool(is_probs, "is_probs")
-        super().__init__()
-        self.blank_idx, self.batch_first, self.is_probs = blank_idx, batch_first, is_probs
-
-    def extra_repr(self) -> str:
-        return ", ".join("{}={}".format(x, getattr(self, x)) for x in self.__constants__)
-
-    def forward(
-        self, logits: torch.Tensor, in_lens: Optional[torch.Tensor] = None
-    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        return ctc_greedy_search(logits, in_lens, self.blank_idx, self.batch_first, self.is_probs)
-
-
-class SequenceLogProbabilities(torch.nn.Module):
-    """Calculate joint log probability of sequences (reference _decoding.py:1636-1720)."""
-
-    __constants__ = "dim", "eos"
-
-    def __init__(self, dim: int = 0, eos: Optional[int] = None):
-        dim = argcheck.is_int(dim, "dim")
-        eos = argcheck.is_int(eos, "eos", True)
-        super().__init__()
-        self.dim, self.eos = dim, eos
-
-    def extra_repr(self) -> str:
-        s = "dim={}".format(self.dim)
-        if self.eos is not None:
-            s += ", eos={}".format(self.eos)
-        return s
-
-    def forward(self, logits: Any, hyp: torch.Tensor) -> torch.Tensor:
-        return sequence_log_probs(logits, hyp, self.dim, self.eos)
-
-
-def _walk_chunk(t: int, max_iters: int) -> int:
-    """How many iterations from ``t``, the first of a chunk, one ``torch.rand((C, N))`` call draws the
-    uniforms of: C = 64, doubling up to 4096 (the chunks start at 0, 64, 192, 448, ...: C = t + 64 until
-    then), cut off at ``max_iters`` -- every route of RandomWalk draws on this schedule."""
-    return min(min(t + 64, 4096), max_iters - t)
-
-
-class RandomWalk(torch.nn.Module):
-    """Perform a random walk on the outputs of a language model (reference
-    _decoding.py:1286-1513).
-
-    On the GPU every token is drawn by one rule (include/pdt_amd.h, "Random walks") from uniforms drawn
-    with torch's generator on the device, ``torch.rand((C, N))`` once per chunk of iterations (C = 64,
-    doubling up to 4096).  Three routes, which draw the same uniforms:
-
-    * a :class:`LookupLanguageModel` whose dense context table is at most 64 MiB, the default hook, no
-      gradients, no initial state: each chunk of iterations is ONE launch over the table
-      (``pdt_random_walk_table``; switch ``PDT_WALK_TABLE``);
-    * any model, the default hook, an output that wants no gradient: the model's call and ONE kernel per
-      iteration (``pydrobert_amd::random_walk_step``: log_softmax, the eos rule, the draw, the state);
-    * a subclass's hook or a model output that wants gradients: the reference's ``log_softmax``, hook and
-      eos masking, then ``pydrobert_amd::random_walk_advance``.
-
-    A LookupLanguageModel gets the same tensors from the first two.  CPU tensors take the reference's loop.
-    """
-
-    __constants__ = ["eos", "default_hook"]
-
-    def __init__(self, lm, eos: Optional[int] = None):
-        eos = argcheck.is_int(eos, "eos", True)
-        super().__init__()
-        if eos is not None:
-            if eos < -lm.vocab_size or eos > lm.vocab_size - 1:
-                raise ValueError(
-                    "Expected eos to be in the range [{}, {}], got {}".format(
-                        -lm.vocab_size, lm.vocab_size - 1, eos
-                    )
-                )
-            eos = (eos + lm.vocab_size) % lm.vocab_size
-        self.lm, self.eos = lm, eos
-        # (a constant: eager and scripted code take the same branches)
-        self.default_hook = type(self).update_log_probs_for_step is RandomWalk.update_log_probs_for_step
-        try:
-            device = next(iter(lm.parameters())).device
-        except StopIteration:
-            device = torch.device("cpu")
-        self.register_buffer("device_buffer", torch.empty(0, device=device))
-
-    def reset_parameters(self) -> None:
-        if hasattr(self.lm, "reset_parameters"):
-            self.lm.reset_parameters()
-
-    def extra_repr(self) -> str:
-        return "eos={}".format(self.eos)
-
-    def update_log_probs_for_step(self, log_probs_prev, log_probs_t, y_prev, y_prev_lens, eos_mask):
-        """Hook (reference _decoding.py:1393-1436); identity by default."""
-        return log_probs_prev, log_probs_t
-
-    @torch.jit.unused
-    def _table_walk(
-        self, prev: Dict[str, torch.Tensor], N: int, max_iters: int
-    ) -> Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]]:
-        """Every chunk of iterations over a LookupLanguageModel's dense context table in ONE launch, the
-        walks' state on the device between chunks and one host wait per chunk (walks still live, the longest
-        walk).  ``None`` when the route does not apply."""
-        lm = self.lm
-        device = self.device_buffer.device
-        if (type(lm) is not LookupLanguageModel or not self.default_hook or len(prev) or N < 1
-                or not switches.get("PDT_WALK_TABLE")):  # fmt: skip
-            return None
-        if torch.is_grad_enabled() and any(p.requires_grad for p in lm.parameters()):
-            return None
-        dense = _dense_table(lm, device)
-        if dense is None:
-            return None
-        table, stats, sos_row, U = dense
-        R, V = table.shape
-        has_eos = self.eos is not None
-        L = _cabi.lib()
-        with torch.no_grad(), _cabi.on_device(device):
-            ctx = torch.full((N,), sos_row, device=device, dtype=torch.long)
-            lens = torch.zeros((N,), device=device, dtype=torch.long)
-            ended = torch.zeros((N,), device=device, dtype=torch.bool)
-            lp = torch.zeros((N,), device=device, dtype=torch.float)
-            ctl = torch.zeros((4,), device=device, dtype=torch.int32)
-            y = torch.empty((0, N), device=device, dtype=torch.long)
-            t, longest, stream = 0, 0, _cabi.stream_ptr(device)
-            while t < max_iters:
-                C = _walk_chunk(t, max_iters)
-                u = torch.rand((C, N), device=device, dtype=torch.float)
-                y_new = torch.empty((t + C, N), device=device, dtype=torch.long)
-                y_new[:t] = y
-                y = y_new
-                _, live, longest = _walk_launch(
-                    device,
-                    lambda host: L.pdt_random_walk_table(
-                        _cabi.ptr(table), table.stride(0), R, U, V, _cabi.ptr(stats), _cabi.ptr(u), N, C,
-                        int(has_eos), int(self.eos or 0), y.data_ptr() + 8 * t * N, _cabi.ptr(ctx), _cabi.ptr(lens),
-                        _cabi.ptr(ended), _cabi.ptr(lp), _cabi.ptr(ctl), host, stream,
-                    ),
-                    "RandomWalk",
-                )  # fmt: skip
-                if has_eos and live == 0:
-                    break
-                t += C
-        # the reference leaves its loop at the first iteration that finds every walk ended
-        T = min(max_iters, longest) if has_eos else max_iters
-        return y[:T], lens, lp
-
-    def _forward_torch(
-        self, prev: Dict[str, torch.Tensor], N: int, max_iters: int
-    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        # the reference's loop (:1466-1507), for CPU tensors
-        device = self.device_buffer.device
-        y = torch.empty((0, N), device=device, dtype=torch.long)
-        prev = self.lm.update_input(prev, y)
-        y_lens = torch.zeros(N, dtype=torch.long, device=device)
-        eos_mask = torch.zeros(N, device=device, dtype=torch.bool)
-        log_probs = torch.zeros(N, device=device)
-        for t in range(max_iters):
-            if bool(eos_mask.all()):
-                break
-            t_ = torch.tensor(t, device=device)
-            lp_t, prev = self.lm.calc_idx_log_probs(y[:t], prev, t_)
-            lp_t = lp_t.log_softmax(-1)
-            log_probs, lp_t = self.update_log_probs_for_step(log_probs, lp_t, y[:t], y_lens, eos_mask)
-            if self.eos is not None:  # ended paths emit eos for free (:1483-1492)
-                lp_t = lp_t.masked_fill(eos_mask.unsqueeze(1), -float("inf"))
-                lp_t[:, self.eos] = lp_t[:, self.eos].masked_fill(eos_mask, 0.0)
-            y, log_probs = random_walk_advance(lp_t, log_probs, y, y_lens)
-            if self.eos is not None:
-                y_lens = y_lens + (~eos_mask).long()
-                eos_mask = y.gather(0, y_lens.unsqueeze(0) - 1).squeeze(0) == self.eos
-            else:
-                y_lens = y_lens + 1
-        return y, y_lens, log_probs
-
-    def forward(
-        self,
-        prev_: Optional[Dict[str, torch.Tensor]] = None,
-        batch_size: Optional[int] = None,
-        max_iters: Optional[int] = None,
-        initial_state: Optional[Dict[str, torch.Tensor]] = None,
-    ):
-        # (``prev_``: the reference's runtime keyword, _decoding.py:1446-1449; ``initial_state``: its
-        # documented call signature -- both are accepted)
-        if initial_state is None:
-            initial_state = prev_
-        prev = dict() if initial_state is None else initial_state
-        device = self.device_buffer.device
-        N = 1 if batch_size is None else batch_size
-        if max_iters is None:
-            if self.eos is None:
-                raise RuntimeError("max_iters must be set when eos is unset")
-            max_iters = 1073741824
-        elif max_iters < 0:
-            raise RuntimeError("max_iters must be non-negative, got {}".format(max_iters))
-        if device.type != "cuda":
-            y, y_lens, log_probs = self._forward_torch(prev, N, max_iters)
-        else:
-            walked: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None
-            if not torch.jit.is_scripting():
-                walked = self._table_walk(prev, N, max_iters)
-            if walked is None:
-                y, y_lens, log_probs = self._forward_hip(prev, N, max_iters)
-            else:
-                y, y_lens, log_probs = walked
-        if batch_size is None:
-            y, y_lens, log_probs = y.squeeze(1), y_lens.squeeze(0), log_probs.squeeze(0)
-        return y, y_lens, log_probs
-
-    def _forward_hip(
-        self, prev: Dict[str, torch.Tensor], N: int, max_iters: int
-    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
-        # The reference's loop (:1466-1507) around any model: the model's call every iteration, then ONE kernel
-        # (pydrobert_amd::random_walk_step) with the default hook and an output that wants no gradient, else the
-        # reference's log_softmax / hook / eos masking and pydrobert_amd::random_walk_advance.  The uniforms of
-        # iterations [t, t + C) come from one torch.rand((C, N)) after the model's call of iteration t (the
-        # chunks of _walk_chunk), and y grows by the chunk.  The one host read per iteration -- whether some
-        # walk is still live -- comes back with the step's kernel: the model is called exactly as often as
-        # under the reference.
-        device = self.device_buffer.device
-        y = torch.empty((0, N), device=device, dtype=torch.long)
-        prev = self.lm.update_input(prev, y)
-        y_lens = torch.zeros(N, dtype=torch.long, device=device)
-        eos_mask = torch.zeros(N, device=device, dtype=torch.bool)
-        log_probs = torch.zeros(N, device=device)
-        ctl = torch.zeros((4,), device=device, dtype=torch.int32)
-        u = torch.empty((0, N), device=device)
-        fused = self.default_hook
-        out_dtype = log_probs.dtype
-        live, u_from, u_to, T = N, 0, 0, 0
-        for t in range(max_iters):
-            if self.eos is not None and live == 0:
-                break
-            t_ = torch.tensor(t, device=device)
-            lp_t, prev = self.lm.calc_idx_log_probs(y[:t], prev, t_)
-            if t == u_to:
-                u_from, u_to = t, t + _walk_chunk(t, max_iters)
-                u = torch.rand((u_to - t, N), device=device, dtype=torch.float)
-                y_new = torch.empty((u_to, N), device=device, dtype=torch.long)
-                y_new[:t] = y[:t]
-                y = y_new
-            fused = fused and not lp_t.requires_grad
-            if fused:
-                out_dtype = torch.promote_types(out_dtype, lp_t.dtype)
-                live = torch.ops.pydrobert_amd.random_walk_step(
-                    lp_t, u[t - u_from], y, t, y_lens, eos_mask, log_probs, ctl, self.eos
-                )
-            else:
-                lp_t = lp_t.log_softmax(-1)
-                log_probs, lp_t = self.update_log_probs_for_step(log_probs, lp_t, y[:t], y_lens, eos_mask)
-                if self.eos is not None:  # ended paths emit eos for free (:1483-1492)
-                    lp_t = lp_t.masked_fill(eos_mask.unsqueeze(1), -float("inf"))
-                    lp_t[:, self.eos] = lp_t[:, self.eos].masked_fill(eos_mask, 0.0)
-                y_t, log_probs = torch.ops.pydrobert_amd.random_walk_advance(
-                    lp_t, u[t - u_from], log_probs, y[:0], None
-                )
-                y = y.index_copy(0, t_.view(1), y_t)  # (not in place: the model may have saved views of y)
-                if self.eos is not None:
-                    y_lens = y_lens + (~eos_mask).long()
-                    eos_mask = eos_mask | (y_t[0] == self.eos)
-                    live = 0 if bool(eos_mask.all()) else 1
-                else:
-                    y_lens = y_lens + 1
-            T = t + 1
-        return y[:T], y_lens, log_probs.to(torch.promote_types(out_dtype, log_probs.dtype))

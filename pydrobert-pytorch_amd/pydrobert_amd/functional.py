@@ -8,12 +8,10 @@ from ._combinatorics import (
     enumerate_vocab_sequences,
     simple_random_sampling_without_replacement,
 )
-from ._decoding import (
-    beam_search_advance,
-    ctc_prefix_search,
-    ctc_prefix_search_advance,
-)
-from ._decoding import ctc_greedy_search, random_walk_advance, sequence_log_probs
+from ._decoding import ctc_prefix_search
+from ._seqops import ctc_greedy_search, sequence_log_probs
+from ._step import beam_search_advance, ctc_prefix_search_advance
+from ._walk import random_walk_advance
 from ._img import (
     dense_image_warp,
     polyharmonic_spline,

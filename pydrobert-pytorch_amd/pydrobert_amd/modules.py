@@ -19,7 +19,8 @@ from ._img import (
 )
 from ._feats import ChunkTokenSequencesBySlices, FeatureDeltas, MeanVarianceNormalization, SliceSpectData
 from ._pad import ChunkBySlices, PadMaskedSequence, PadVariable
-from ._decoding import CTCGreedySearch, RandomWalk, SequenceLogProbabilities
+from ._seqops import CTCGreedySearch, SequenceLogProbabilities
+from ._walk import RandomWalk
 from ._rl import TimeDistributedReturn
 from ._lm import (
     ExtractableSequentialLanguageModel,

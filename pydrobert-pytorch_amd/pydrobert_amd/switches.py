@@ -22,7 +22,7 @@ _HOST_DEFAULTS = {
     "PDT_CTC_LM_FUSED": 1,  # CTCPrefixSearch + LookupLanguageModel: every frame from one call of the library (0: the host's frame loop)
     "PDT_CTC_LM_TABLE": 1,  # ... a bigram model's factor rows from a table built once per model (csrc/ctc_lm_table.hip)
     "PDT_BEAM_FUSED": 1,  # BeamSearch: one kernel per iteration
-    "PDT_BEAM_SEARCH": 1,  # ... and every iteration from ONE launch, the paths read off a trie at the end (csrc/beam_step.hip)
+    "PDT_BEAM_SEARCH": 1,  # ... and every iteration from ONE launch, the paths read off a trie at the end (csrc/beam_search_table.hip)
     "PDT_BEAM_TABLE": 1,  # BeamSearch over a bigram LookupLanguageModel reads its dense table
     "PDT_CHECK_INVARIANTS": 0,  # BeamSearch's loop checks that the history grows (a host read per iteration)
     "PDT_WALK_TABLE": 1,  # RandomWalk over a LookupLanguageModel: chunks of iterations over its dense context table, one launch each

@@ -6,7 +6,7 @@ for p in (ROOT, os.path.join(ROOT, "pydrobert-pytorch_amd"), os.path.join(ROOT, 
     sys.path.insert(0, p)
 import numpy as np, torch, warnings
 import oracle
-from pydrobert_amd import _decoding as D, functional as F
+from pydrobert_amd import _step as D, functional as F
 warnings.simplefilter("ignore")
 dev = "cuda"
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)

@@ -505,7 +505,7 @@ def test_ctc_step_forms_the_extension_probabilities_itself(device, V, W):
     own; both mixtures.  V = 1025 is past the kernel's rows: the operator makes the two calls itself.
     Also here: prefixes that share one expand()ed row of extension probabilities share one list
     (PDT_STEP_FLAT) -- same outputs as with a row each."""
-    from pydrobert_amd import _decoding as D
+    from pydrobert_amd import _step as D
 
     g = torch.Generator(device=device).manual_seed(V * 31 + W)
     N, T = 5, 14
@@ -540,6 +540,108 @@ def test_ctc_step_forms_the_extension_probabilities_itself(device, V, W):
             for i, (u, v) in enumerate(zip(flat(shared), flat(each))):
                 assert torch.equal(u, v), ("shared", V, W, t, i)
             y, last, lens, nb, b, isp = two[0], two[1], two[2], two[3], two[4], two[5]
+
+
+def _ctc_state(rng, N, V, Kp):
+    """A beam of Kp prefixes per batch element: the oracle's first frame from the empty prefix."""
+    p = rng.dirichlet(np.ones(V + 1), N).astype(np.float32)
+    nonext, blank = np.ascontiguousarray(p[:, :V]), np.ascontiguousarray(p[:, V])
+    out = oracle.ctc_prefix_search_advance(
+        (nonext[:, None].copy(), nonext, blank), Kp, (np.zeros((N, 1), np.float32), np.ones((N, 1), np.float32)),
+        np.zeros((0, N, 1), np.int64), np.zeros((N, 1), np.int64), np.zeros((N, 1), np.int64), np.ones((N, 1, 1), bool),
+    )  # fmt: skip
+    return out[0], out[1], out[2], out[3], out[4]
+
+
+def _ctc_frame_inputs(rng, N, V, Kp):
+    p = np.exp(rng.normal(size=(N, V + 1)) * 1.5).astype(np.float32)
+    p /= p.sum(1, keepdims=True)
+    nonext, blank = np.ascontiguousarray(p[:, :V]), np.ascontiguousarray(p[:, V])
+    lm = np.exp(rng.normal(size=(N, Kp, V)) * 0.7).astype(np.float32)
+    lm /= lm.sum(2, keepdims=True)
+    return (lm ** 0.5 * nonext[:, None]).astype(np.float32), nonext, blank
+
+
+@pytest.mark.parametrize("Kp", [3, 9, 17])
+def test_ctc_prefix_search_advance_waves_per_element(device, Kp):
+    """The waves of a workgroup take the K' prefixes in turn, a power of two <= min(K', 8) of them: K' = 3
+    (two waves, an odd prefix left over), 9 (eight waves, one prefix in a second round) and 17 (eight waves,
+    three rounds, the last with one) at N = 2, V = 70, two frames each against the oracle.  (K' = 1, 2 and 8
+    are what test_ctc_prefix_search_advance_teacher_forced's widths 2 and 8 already run.)"""
+    rng = np.random.default_rng(9000 + Kp)
+    N, V = 2, 70
+    y, last, lens, (nb, b), isp = _ctc_state(rng, N, V, Kp)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    for t in range(2):
+        assert nb.shape[1] == Kp
+        ext, nonext, blank = _ctc_frame_inputs(rng, N, V, Kp)
+        exp = oracle.ctc_prefix_search_advance((ext, nonext, blank), Kp, (nb, b), y, last, lens, isp)
+        act = F.ctc_prefix_search_advance(
+            (tt(ext), tt(nonext), tt(blank)), Kp, (tt(nb), tt(b)), tt(y), tt(last), tt(lens), tt(isp)
+        )
+        _cmp_ctc_step(act, exp, (Kp, t))
+        y, last, lens, (nb, b), isp = exp[0], exp[1], exp[2], exp[3], exp[4]
+
+
+@pytest.mark.parametrize("Kp", [2, 9, 17])
+def test_ctc_step_with_lm_scores_waves_per_element(device, Kp):
+    """The step that mixes the language model's scores itself runs at most four waves per element: K' = 2
+    (two waves), 9 and 17 (four waves, three and five rounds, the last with one prefix) at N = 2, V = 70, both
+    mixtures, against the oracle's step on fusion_ext's extension probabilities.  (K' = 1, 3 and 8 are what
+    test_ctc_step_forms_the_extension_probabilities_itself's widths already run.)"""
+    from pydrobert_amd import _step as D
+
+    rng = np.random.default_rng(9100 + Kp)
+    N, V = 2, 70
+    y, last, lens, (nb, b), isp = _ctc_state(rng, N, V, Kp)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    for valid_mixture in (False, True):
+        _, nonext, blank = _ctc_frame_inputs(rng, N, V, Kp)
+        lm = torch.from_numpy((rng.normal(size=(N, Kp, V)) * 2.0).astype(np.float32)).to(device)
+        ext = torch.ops.pydrobert_amd.fusion_ext(lm.reshape(N * Kp, V), tt(nonext), tt(blank), 0.3, valid_mixture)
+        exp = oracle.ctc_prefix_search_advance((ext.cpu().numpy(), nonext, blank), Kp, (nb, b), y, last, lens, isp)
+        o = D._ctc_step_with_lm_scores(
+            lm, 0.3, valid_mixture, tt(nonext), tt(blank), Kp, tt(nb), tt(b), tt(y), tt(last), tt(lens), tt(isp)
+        )
+        _cmp_ctc_step((o[0], o[1], o[2], (o[3], o[4]), o[5], o[6], o[7]), exp, (Kp, valid_mixture))
+
+
+def test_ctc_prefix_search_advance_row_beyond_64k_of_lds(device):
+    """ctc_advance_kernel<false> keeps the frame's row of V + 1 probabilities in LDS: at V = 16 400, width 2
+    that is 65 616 bytes of row + 1 056 (K' = 1) or 1 568 (K' = 2) of frame scratch + 512 per wave = 67 184
+    bytes in the first frame and 68 208 in the next two -- above the 64 KiB a kernel gets without asking.
+    N = 1, three frames, against the oracle."""
+    rng = np.random.default_rng(16400)
+    N, V, W = 1, 16400, 2
+    nb, b = np.zeros((N, 1), np.float32), np.ones((N, 1), np.float32)
+    y = np.zeros((0, N, 1), np.int64)
+    last = lens = np.zeros((N, 1), np.int64)
+    isp = np.ones((N, 1, 1), bool)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    for t in range(3):
+        ext, nonext, blank = _ctc_frame_inputs(rng, N, V, nb.shape[1])
+        exp = oracle.ctc_prefix_search_advance((ext, nonext, blank), W, (nb, b), y, last, lens, isp)
+        act = F.ctc_prefix_search_advance(
+            (tt(ext), tt(nonext), tt(blank)), W, (tt(nb), tt(b)), tt(y), tt(last), tt(lens), tt(isp)
+        )
+        _cmp_ctc_step(act, exp, t)
+        y, last, lens, (nb, b), isp = exp[0], exp[1], exp[2], exp[3], exp[4]
+
+
+def test_ctc_prefix_search_advance_wide_beyond_64k_of_lds(device):
+    """ctc_advance_wide_kernel's LDS is 16 K + 9 280 + 56 K' + 16 width bytes, K = min(width, K' (V + 1)): a beam
+    of K' = 40 prefixes (V = 70) widened to 1 700 takes 27 200 + 9 280 + 2 240 + 27 200 = 65 920 bytes -- above the
+    64 KiB a kernel gets without asking.  N = 1, against the oracle."""
+    rng = np.random.default_rng(1700)
+    N, V, Kp, W = 1, 70, 40, 1700
+    y, last, lens, (nb, b), isp = _ctc_state(rng, N, V, Kp)
+    ext, nonext, blank = _ctc_frame_inputs(rng, N, V, Kp)
+    exp = oracle.ctc_prefix_search_advance((ext, nonext, blank), W, (nb, b), y, last, lens, isp)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)  # noqa: E731
+    act = F.ctc_prefix_search_advance(
+        (tt(ext), tt(nonext), tt(blank)), W, (tt(nb), tt(b)), tt(y), tt(last), tt(lens), tt(isp)
+    )
+    _cmp_ctc_step(act, exp, "wide")
 
 
 @pytest.mark.parametrize("with_lens", [False, True])
@@ -666,6 +768,53 @@ def test_beam_search_advance_wider_than_a_wave(device):
             valid = np.arange(exp[0].shape[0])[:, None, None] < exp[1][None]
             valid[..., K:] = False
             assert np.array_equal(np.where(valid, act[0], 0), np.where(valid, exp[0], 0)), (it, with_lens)
+
+
+def _cmp_beam_step(act, exp, K, what):
+    act = [x.cpu().numpy() for x in act]
+    assert act[0].shape == exp[0].shape, (what, act[0].shape, exp[0].shape)
+    assert np.array_equal(act[1], exp[1]) and np.array_equal(act[3], exp[3]), what
+    assert np.array_equal(act[2], exp[2]), what  # float adds are the same single operation
+    valid = np.arange(exp[0].shape[0])[:, None, None] < exp[1][None]
+    valid[..., K:] = False
+    assert np.array_equal(np.where(valid, act[0], 0), np.where(valid, exp[0], 0)), what
+
+
+@pytest.mark.parametrize("Kp", [1, 2, 3, 8, 9, 17])
+def test_beam_search_advance_waves_per_element(device, Kp):
+    """The list form's waves take the K' prefixes in turn, a power of two <= min(K', 8) of them: one wave,
+    two, two with a prefix left over, eight, eight with one prefix in a second round, eight with three rounds
+    -- N = 2, V = 70, with lengths, against the oracle.  Rows with a token stride of 2 take the list form; the
+    same values in contiguous rows (the flat form, eight waves whatever K') must give the same."""
+    rng = np.random.default_rng(9200 + Kp)
+    N, V, W, S = 2, 70, 11, 4
+    lpt = np.log(rng.dirichlet(np.ones(V), (N, Kp))).astype(np.float32)
+    lpp = rng.normal(size=(N, Kp)).astype(np.float32)
+    yp = rng.integers(0, V, (S, N, Kp))
+    ypl = rng.integers(0, S + 1, (N, Kp))
+    exp = oracle.beam_search_advance(lpt, W, lpp, yp, ypl)
+    tt = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+    strided = torch.zeros((N, Kp, 2 * V), device=device)
+    strided[..., ::2] = tt(lpt)
+    for rows in (strided[..., ::2], tt(lpt)):
+        act = F.beam_search_advance(rows, W, tt(lpp), tt(yp), tt(ypl))
+        _cmp_beam_step(act, exp, min(W, Kp * V), (Kp, rows.stride()))
+
+
+def test_beam_search_advance_wide_beyond_64k_of_lds(device):
+    """beam_advance_wide_kernel's LDS is 16 K + 9 280 + 12 width bytes, K = min(width, K' V): width 2 048 over
+    K' V = 3 x 700 candidates takes 32 768 + 9 280 + 24 576 = 66 624 bytes -- above the 64 KiB a kernel gets
+    without asking.  N = 1, against the oracle."""
+    rng = np.random.default_rng(2048)
+    N, Kp, V, W, S = 1, 3, 700, 2048, 2
+    lpt = np.log(rng.dirichlet(np.ones(V), (N, Kp))).astype(np.float32)
+    lpp = rng.normal(size=(N, Kp)).astype(np.float32)
+    yp = rng.integers(0, V, (S, N, Kp))
+    ypl = rng.integers(0, S + 1, (N, Kp))
+    exp = oracle.beam_search_advance(lpt, W, lpp, yp, ypl)
+    tt = lambda a: torch.from_numpy(a).to(device)  # noqa: E731
+    act = F.beam_search_advance(tt(lpt), W, tt(lpp), tt(yp), tt(ypl))
+    _cmp_beam_step(act, exp, W, "wide")
 
 
 def test_beam_search_advance_errors(device):

@@ -7,7 +7,7 @@ T, N, V, K = 512, 4096, 256, 16
 L = _cabi.lib()
 names = ["producer frames", "short list", "miss: too few", "miss: too many", "consumer completes", "lean tier fails", "third entry wins: 1 prefix", "third entry wins: several"]
 def stats(lg, tag):
-    buf = (ctypes.c_ulonglong * 16)()
+    buf = (ctypes.c_ulonglong * 24)()
     L.pdt_debug_read_stats(buf, 1)
     y, yl, yp = F.ctc_prefix_search(lg, K); torch.cuda.synchronize()
     L.pdt_debug_read_stats(buf, 1)

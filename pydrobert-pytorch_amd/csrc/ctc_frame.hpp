@@ -22,9 +22,10 @@ __device__ unsigned long long *g_stamp_lds_dummy;
 #define PDT_STAMP_BEGIN do {} while (0)
 #endif
 
-// Diagnostic build only (-DPDT_STATS): event counters (lane 0 of every wave)
+// Diagnostic build only (-DPDT_STATS): event counters (lane 0 of every wave; [16]: frames the steady
+// tier of ctc_frame decided)
 #ifdef PDT_STATS
-__device__ unsigned long long g_stats[16];
+__device__ unsigned long long g_stats[24];
 #define PDT_STAT(i) do { if (lane_id() == 0) atomicAdd(&g_stats[i], 1ull); } while (0)
 #else
 #define PDT_STAT(i) do {} while (0)
@@ -67,6 +68,9 @@ struct CtcArgs {
   // PDT_CTC_LEAN_EXTRA=0: frames the lean tier's mid / exact paths would decide go to the full tiers
   // (same results; the tests compare the two)
   int no_lean_extra;
+  // PDT_CTC_STEADY=0: no frame is decided by the steady tier in front of the lean tier's sort (same
+  // results, same kernel instance; the tests compare the two).  Shared-list searches only.
+  int no_steady;
 };
 
 struct Beam {
@@ -362,6 +366,9 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
   // a lower bound of the K-th winner's key the lean tier leaves behind for the full tiers
   // (0: none): its candidates are a subset of theirs, so its K-th largest cannot exceed theirs
   unsigned tau_hint = 0u;
+  // the steady tier decided the frame: new entry i is old entry i extended (the state update below
+  // then needs none of its fetches by source lane)
+  bool steady_f = false;
   {  // scope of the lean tier's per-lane layout values
   // All 64 lanes hold candidates: lane = G * r + k carries, for prefix k, three of its
   // candidates (slots s = 0..2, "entry" e = r + R * s): entries 0 .. 3R-3 are the first
@@ -409,6 +416,47 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
     // their rounded keys are >= 64).
     PDT_STAMP(7);
     const unsigned kt = has ? (((keyL + 63u) & ~63u) | (63u - (unsigned)lane)) : (63u - (unsigned)lane);
+    // Steady tier: the beam is kept in rank order, so row 0 (every prefix's best available extension:
+    // tot_k, non-increasing in k, times ONE list probability unless merges took entries away) is usually
+    // sorted already, and in most frames of a full beam it beats everything else -- a challenger gets in
+    // only by beating the K-th mass.  Then the sort's result is known without sorting: rank i is lane i.
+    // Decided on the sort's own buckets (kt >> 6): lanes 0 .. K-1 hold real row-0 candidates (no upper
+    // bound of a hidden entry), their buckets descend STRICTLY in lane order (no rounded tie among
+    // them), and the bucket of lane K-1 is strictly above every bucket of rows 1-3 (bounds included:
+    // they only make the test stricter) -- which is also what `tie` below asks of ranks K-1 and K.
+    // No row-1 entry wins, nothing ties, no bound wins: the lean tier would select exactly these.
+    // (wave-uniform: ballots, readlanes and scalar compares; one branch with all that depends on it inside)
+    // Shared-list forms only (ctc_search.hip, ctc_rowreg.hip): the conditions hold for per-prefix lists
+    // just as well, but the step functions and the bigram-table search carry no switch to compare with.
+    bool steady = false;
+    // (the switch in the outer condition: as the last term of `steady` it cost twenty more scalar spills)
+    if (!DENSE && K <= 16 && !a.no_steady) {
+      const unsigned bk = kt >> 6;
+      const unsigned bk_next = (unsigned)__builtin_amdgcn_mov_dpp((int)bk, 0x101, 0xf, 0xf, true);  // row_shl:1
+      const unsigned first_k = (1u << K) - 1u;
+      const unsigned row0_has = (unsigned)__ballot(has) & 0xFFFFu, row0_hid = (unsigned)__ballot(hidden) & first_k;
+      const unsigned desc = (unsigned)__ballot(bk > bk_next) & (first_k >> 1);
+      unsigned rmax = bk;  // row maxima in lanes 15, 31, 47, 63
+      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(1)>((int)rmax, 0));
+      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(2)>((int)rmax, 0));
+      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(4), 0xf, 0xe>((int)rmax, 0));
+      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(8), 0xf, 0xc>((int)rmax, 0));
+      const unsigned rest = max(max((unsigned)__builtin_amdgcn_readlane((int)rmax, 31), (unsigned)__builtin_amdgcn_readlane((int)rmax, 47)),
+                                (unsigned)__builtin_amdgcn_readlane((int)rmax, 63));
+      const unsigned kth = (unsigned)__builtin_amdgcn_readlane((int)bk, K - 1);
+      steady = row0_has == first_k && row0_hid == 0u && desc == (first_k >> 1) && kth > rest;
+    }
+    if (steady) {
+      PDT_STAT(16);
+      steady_f = true;
+      if (lane < K) {
+        new_src = lane;
+        new_tok = tokL;
+        new_kind = 0;
+        new_mass = fkey_nonneg_inv(keyL);
+      }
+      selected = true;
+    } else {  // the sort decides (not indented: the lean tier as it was)
     const unsigned st = wave_sort_desc<unsigned>(kt);
     PDT_STAMP(8);
     int wl = 63 - (int)(st & 63u);
@@ -558,6 +606,7 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
       }
       selected = true;
     }
+    }  // !steady
   }
 
   }
@@ -596,16 +645,23 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
   // last probability, key + 1): if a bound is ever taken as a winner the list is completed and
   // the tiers run again; otherwise the short list was all this frame needed.
   auto fill_main = [&](bool mine) {
+    // (shared lists: the row recomputed, laundered -- kept across the tiers it was spilled to scratch and
+    // reloaded here.  The per-prefix-list kernels are left as they were.)
+    int rr_m = rr;
+    if (!DENSE) {
+      rr_m = lane >> (G == 16 ? 4 : 5);
+      asm volatile("" : "+v"(rr_m));
+    }
     const int list_k = list_of(ksrc);
     const int *lt = L.tl_tok + list_k * PDT_WAVE;
     const float *lp = L.tl_p + list_k * PDT_WAVE;
     if (M <= 32) {  // the usual case (K + K' <= 32): half the work per bit operation
       unsigned av = (unsigned)shfl_i((int)(unsigned)avail, ksrc);
       const int n_av = __popc(av);
-      for (int i = 0; i < rr; ++i) av &= av - 1u;
+      for (int i = 0; i < rr_m; ++i) av &= av - 1u;
 #pragma unroll
       for (int sl = 0; sl < 3; ++sl) {
-        const int e = rr + R * sl;
+        const int e = rr_m + R * sl;
         unsigned key = 0u;
         int tok = 0;
         if (e < n_main && av != 0u && kvalid) {
@@ -626,10 +682,10 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
       return;
     }
     u64 av = shfl_u64(avail, ksrc);
-    for (int i = 0; i < rr; ++i) av &= av - 1ull;  // skip to entry rr
+    for (int i = 0; i < rr_m; ++i) av &= av - 1ull;  // skip to entry rr
 #pragma unroll
     for (int sl = 0; sl < 3; ++sl) {
-      const int e = rr + R * sl;
+      const int e = rr_m + R * sl;
       unsigned key = 0u;
       int tok = 0;
       if (e < n_main && av != 0ull && kvalid) {
@@ -823,9 +879,15 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
   PDT_STAMP(3);
   // ---- new beam state of lane i (:868-880) ---------------------------------------------
   const int srcl = new_kind >= 0 ? new_src : lane;
-  const float NB_s = shfl_f(NB, srcl), B_s = shfl_f(B, srcl);
-  const int last_s = shfl_i(lastc, srcl), len_s = shfl_i(bm.len, srcl), node_s = shfl_i(bm.node, srcl);
-  const unsigned isp_s = (unsigned)shfl_i((int)bm.isp, srcl);
+  // (a steady frame: srcl is the lane itself, the seven fetches are identities)
+  float NB_s = NB, B_s = B;
+  int last_s = lastc, len_s = bm.len, node_s = bm.node;
+  unsigned isp_s = bm.isp;
+  if (!steady_f) {
+    NB_s = shfl_f(NB, srcl), B_s = shfl_f(B, srcl);
+    last_s = shfl_i(lastc, srcl), len_s = shfl_i(bm.len, srcl), node_s = shfl_i(bm.node, srcl);
+    isp_s = (unsigned)shfl_i((int)bm.isp, srcl);
+  }
   const bool is_ext = new_kind == 0 || new_kind == 1;
   const bool is_valid = new_kind >= 0;
   Beam nw;
@@ -834,7 +896,7 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
   nw.last = !is_valid ? 0 : (is_ext ? new_tok : last_s);
   nw.len = !is_valid ? 0 : len_s + (is_ext ? 1 : 0);
   nw.node = !is_valid ? -1 : (is_ext ? t * W + lane : node_s);
-  if (TRIE) nw.origin = shfl_i(bm.origin, srcl);
+  if (TRIE) nw.origin = steady_f ? bm.origin : shfl_i(bm.origin, srcl);
   if (TRIE && is_valid && is_ext)
     // (uniform base + 32-bit byte offset: T * W * 8 < 2^32 is checked on the host.  The full
     // 64-bit index was ~20 scalar instructions and five reloads of spilled scalars per frame.)
@@ -846,10 +908,13 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
   // from old entry j, so lane a visits  U_{j in isp(src_a)} chm[j]  (usually 1-3 entries).
   // nxt[a * W + b] = token of prefix b at position len(a), defined when a is a strict prefix.
   const int RS = W > Kp ? W : Kp;
-  if (lane < RS) L.chm[lane] = fresh_zero();
-  wave_sync();
+  // (a steady frame: chm[j] would be 1 << j -- the table is neither built nor read)
+  if (!steady_f) {
+    if (lane < RS) L.chm[lane] = fresh_zero();
+    wave_sync();
+    if (is_valid) atomicOr(&L.chm[new_src], 1u << lane);
+  }
   if (is_valid) {
-    atomicOr(&L.chm[new_src], 1u << lane);
     L.info[2 * lane] = new_tok;
     L.info[2 * lane + 1] = len_s | (new_src << 20) | ((is_ext ? 1 : 0) << 28);
   }
@@ -916,7 +981,9 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
 #endif
   if (is_valid && !pairs_done) {
     unsigned cand = 0u;
-    for (unsigned m = isp_s; m; m &= m - 1u) cand |= L.chm[__builtin_ctz(m)];
+    if (steady_f) cand = isp_s;  // (every old entry j has the one descendant j)
+    else
+      for (unsigned m = isp_s; m; m &= m - 1u) cand |= L.chm[__builtin_ctz(m)];
     // (an entry is a prefix of itself and never its own strict prefix: one iteration less for every
     // lane, i.e. for the wave -- ~26 instructions of the ~300 a lean frame takes)
     cand &= ~(1u << lane);

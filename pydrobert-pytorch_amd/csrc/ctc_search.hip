@@ -906,6 +906,7 @@ int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, 
   a.grow = reinterpret_cast<unsigned char *>(workspace) + ctc_trie_bytes(T, N, width);
   a.exact_div = switches().ctc_exact_div == 1 ? 1 : 0;
   a.no_lean_extra = switches().ctc_lean_extra == 0 ? 1 : 0;
+  a.no_steady = switches().ctc_steady == 0 ? 1 : 0;  // (no part of the plan: both values take the same instance)
   // (contiguous rows: the register form addresses a row as base + immediates)
   if (ctc_rowreg_applies(a.V, a.W) && lg_sv == 1) return launch_ctc_rowreg(a, (hipStream_t)stream);
   CtcPlan plan;
@@ -920,10 +921,10 @@ int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, 
 }  // extern "C"
 
 #ifdef PDT_STATS
-extern "C" int pdt_debug_read_stats(unsigned long long *host16, int reset) {
-  hipError_t e = hipMemcpyFromSymbol(host16, HIP_SYMBOL(pdt::g_stats), sizeof(unsigned long long) * 16);
+extern "C" int pdt_debug_read_stats(unsigned long long *host24, int reset) {
+  hipError_t e = hipMemcpyFromSymbol(host24, HIP_SYMBOL(pdt::g_stats), sizeof(unsigned long long) * 24);
   if (e == hipSuccess && reset) {
-    unsigned long long z[16] = {0};
+    unsigned long long z[24] = {0};
     e = hipMemcpyToSymbol(HIP_SYMBOL(pdt::g_stats), z, sizeof(z));
   }
   return (int)e;

@@ -16,6 +16,8 @@ struct Switches {
   int step_flat;       // PDT_STEP_FLAT      1  step functions: one selection over all K' * V candidates (beam) / one list for prefixes that share
                        //                       their extension row (CTC) (0: a sorted list per prefix; same results)
   int ctc_lean_extra;  // PDT_CTC_LEAN_EXTRA 1  CTC frame: one-prefix and tie frames decided beside the lean tier (0: by the full tiers, same results)
+  int ctc_steady;      // PDT_CTC_STEADY     1  CTC search without a model: frames whose best extensions are in rank order and beat everything
+                       //                       else skip the lean tier's sort (0: every lean frame sorts; same kernel instance, same bits)
 };
 
 Switches &switches();

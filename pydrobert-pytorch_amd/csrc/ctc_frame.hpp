@@ -420,31 +420,39 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
     // tot_k, non-increasing in k, times ONE list probability unless merges took entries away) is usually
     // sorted already, and in most frames of a full beam it beats everything else -- a challenger gets in
     // only by beating the K-th mass.  Then the sort's result is known without sorting: rank i is lane i.
-    // Decided on the sort's own buckets (kt >> 6): lanes 0 .. K-1 hold real row-0 candidates (no upper
-    // bound of a hidden entry), their buckets descend STRICTLY in lane order (no rounded tie among
-    // them), and the bucket of lane K-1 is strictly above every bucket of rows 1-3 (bounds included:
-    // they only make the test stricter) -- which is also what `tie` below asks of ranks K-1 and K.
-    // No row-1 entry wins, nothing ties, no bound wins: the lean tier would select exactly these.
+    // Decided on the EXACT keys keyL: lanes 0 .. K-1 hold real row-0 candidates (no upper bound of a
+    // hidden entry), their keys do not increase in lane order, and the key of lane K-1 is STRICTLY above
+    // every key of rows 1-3 (bounds take part with their + 1: stricter only).  Equal or nearly equal
+    // keys among lanes 0 .. K-1 are in place all the same: where the rounded sort ties, the lean tier
+    // ranks by exact key and then by the full tiers' tie order, the lowest flat candidate index
+    // (trank below) -- for a row-0 candidate kb * 128 + 2 j + 1, which grows with the lane whatever j
+    // is, so lane order is the order it would produce (a pair of prefixes that came by equal masses
+    // once ties in every later frame, and on the sort's buckets each of those frames paid the sort,
+    // the pair fix-up and the fetches to get back what was there).  An equal key in rows 1-3 may have
+    // the lower index (a row-1 entry of a lower prefix has): equality there must not pass.  Masses that
+    // have underflowed into the lowest bucket stay with the sort and the full tiers (the K-th key must
+    // lie above it; the lean tier asks the same of its ties).
+    // No row-1 entry wins, no bound wins, no tie is out of place: the lean tier would select exactly these.
     // (wave-uniform: ballots, readlanes and scalar compares; one branch with all that depends on it inside)
     // Shared-list forms only (ctc_search.hip, ctc_rowreg.hip): the conditions hold for per-prefix lists
     // just as well, but the step functions and the bigram-table search carry no switch to compare with.
     bool steady = false;
     // (the switch in the outer condition: as the last term of `steady` it cost twenty more scalar spills)
     if (!DENSE && K <= 16 && !a.no_steady) {
-      const unsigned bk = kt >> 6;
-      const unsigned bk_next = (unsigned)__builtin_amdgcn_mov_dpp((int)bk, 0x101, 0xf, 0xf, true);  // row_shl:1
+      const unsigned key_next = (unsigned)__builtin_amdgcn_mov_dpp((int)keyL, 0x101, 0xf, 0xf, true);  // row_shl:1
       const unsigned first_k = (1u << K) - 1u;
       const unsigned row0_has = (unsigned)__ballot(has) & 0xFFFFu, row0_hid = (unsigned)__ballot(hidden) & first_k;
-      const unsigned desc = (unsigned)__ballot(bk > bk_next) & (first_k >> 1);
-      unsigned rmax = bk;  // row maxima in lanes 15, 31, 47, 63
+      const unsigned desc = (unsigned)__ballot(keyL >= key_next) & (first_k >> 1);
+      unsigned rmax = keyL;  // row maxima in lanes 15, 31, 47, 63
       rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(1)>((int)rmax, 0));
       rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(2)>((int)rmax, 0));
       rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(4), 0xf, 0xe>((int)rmax, 0));
       rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(8), 0xf, 0xc>((int)rmax, 0));
       const unsigned rest = max(max((unsigned)__builtin_amdgcn_readlane((int)rmax, 31), (unsigned)__builtin_amdgcn_readlane((int)rmax, 47)),
                                 (unsigned)__builtin_amdgcn_readlane((int)rmax, 63));
-      const unsigned kth = (unsigned)__builtin_amdgcn_readlane((int)bk, K - 1);
-      steady = row0_has == first_k && row0_hid == 0u && desc == (first_k >> 1) && kth > rest;
+      const unsigned kth = (unsigned)__builtin_amdgcn_readlane((int)keyL, K - 1);
+      // (64: the largest key of the lowest bucket)
+      steady = row0_has == first_k && row0_hid == 0u && desc == (first_k >> 1) && kth > max(rest, 64u);
     }
     if (steady) {
       PDT_STAT(16);
@@ -463,6 +471,10 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
     unsigned wkey = (unsigned)shfl_i((int)keyL, wl);
     const unsigned st_next = (unsigned)shfl_i((int)st, lane + 1);
     bool tie = lane < K && (st >> 6) != 0u && (st >> 6) == (st_next >> 6);
+#ifdef PDT_UTT_REASONS  // (counted here: the exact re-ranking below settles most of them and clears the flag)
+    if (__ballot(tie) != 0ull) PDT_UTT(2, 1);
+    if (__ballot(tie && (st >> 6) == 1u) != 0ull) PDT_UTT(3, 1);
+#endif
 #ifndef PDT_NO_EXACT_LEAN
     // Two of the first K + 1 agree in the upper 26 bits.  Between prefixes that came by equal masses
     // once (two tokens with the same logit in one frame is all it takes) this repeats in every later
@@ -506,10 +518,6 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
     const int wid = wth < 0 ? 64 : 0;
     PDT_STAMP(9);
     bool lean_ok = __ballot((isw && wid >= 64) || tie) == 0ull;
-#ifdef PDT_UTT_REASONS
-    if (__ballot(tie) != 0ull) PDT_UTT(2, 1);
-    if (__ballot(tie && (st >> 6) == 1u) != 0ull) PDT_UTT(3, 1);
-#endif
     if (__ballot(isw && wid >= 64) == 0ull) {
       // (not when an upper bound ranks among the first K: that is no real candidate.)  The keys
       // of a bucket of the rounded sort lie in (r - 64, r].
@@ -819,11 +827,20 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
     const unsigned lk = max(max(key0, key1), key2);
     const unsigned mx = wave_max_u32(lk);
     if (mx == 0u) break;  // fewer valid candidates than K: the rest stay invalid (:902-924)
-    const int sw_l = key0 == mx ? 0 : (key1 == mx ? 1 : 2);
-    const int tw_l = key0 == mx ? tk0 : (key1 == mx ? tk1 : tk2);
+    int sw_l = key0 == mx ? 0 : (key1 == mx ? 1 : 2);
+    int tw_l = key0 == mx ? tk0 : (key1 == mx ? tk1 : tk2);
     const u64 at_max = __ballot(lk == mx);
     int win = (int)__builtin_ctzll(at_max);
-    if ((at_max & (at_max - 1ull)) && mx > 1u) {  // several lanes hold the (non-zero) maximum: lowest flat index first
+    // several lanes hold the (non-zero) maximum: lowest flat index first.  A lane's own slots may tie as well:
+    // its stream-0 entries rank in slot order, but slot 2 of row R-2 is the last-token stream, and within one
+    // prefix the flat index is the token's -- the stream goes first if its token is the lower.  (In frame 0 it
+    // is token 0 for the empty prefix, with the mass of an extension: it ties with whatever shares its logit.)
+    const u64 s1_max = __ballot(key2 == mx) & (((1ull << G) - 1ull) << (G * (R - 2)));
+    if (((at_max & (at_max - 1ull)) || s1_max) && mx > 1u) {
+      if (rr == R - 2 && key2 == mx && tk2 < tw_l) {  // (slot 2 chosen already: tk2 == tw_l)
+        sw_l = 2;
+        tw_l = tk2;
+      }
       const unsigned inv = lk == mx ? ~((tie_rank(sw_l, tw_l) << 6) | (unsigned)lane) : 0u;
       win = (int)(~wave_max_u32(inv) & 63u);
     }

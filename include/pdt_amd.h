@@ -874,6 +874,37 @@ int pdt_enumerate_cardinality(const int64_t *length, const int64_t *count, int64
 int pdt_srswor(const int64_t *total_count, const int64_t *given_count, const float *u, int64_t B,
                int64_t out_size, float *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Relaxed sampling (reference _straight_through.py:251-598): one launch per method of the Gumbel /
+ * one-hot categorical relaxation and of the logistic / Bernoulli one.  dtype 0 float32, 1 float64.
+ * in1, in2 and out are R dense rows of V elements (out is (R,) for the Gumbel methods that reduce);
+ * sample row r reads parameter row r mod B at param[(r mod B) * p_sr + j * p_sv].  The noise comes in
+ * as data: u and v are clamped to [eps, 1 - eps] of the dtype, as are the probabilities.
+ *   op  method     param   in1    in2  out
+ *   0   rsample    logits  u      -    z      Gumbel: logits - log(-log u); logistic: logits + log u - log1p(-u)
+ *   1   threshold  -       z      -    b      Gumbel: one-hot of the row arg-max (lowest index of a tie, -0 ties
+ *                                             with +0, a NaN is the maximum); logistic: z >= 0
+ *   2   tlog_prob  logits  b      -    lp     Gumbel (R,): sum_j [b_j != 0] logits_j; logistic: b logits - softplus(logits)
+ *   3   csample    probs   b      v    zcond  Gumbel: k the first nonzero of b, z_k = -log(-log v_k), else
+ *                                             min(z_k - eps, -log(-log v_j / p_j - log v_k)); logistic: lines 368-375
+ *   4   log_prob   logits  z      -    lp     Gumbel (R,): sum_j g - exp g, g = logits - z; logistic: lines 340-347
+ *   5   clog_prob  logits  zcond  b    lp     Gumbel (R,), lines 558-577, -inf unless b is the one-hot of zcond's
+ *                                             arg-max; logistic: lines 377-393, -inf where (zcond >= 0) != b
+ * R == 0 or V == 0 is OK (nothing to do).  PDT_E_TOO_LONG when V exceeds 2^31 - 65.
+ * pdt_relaxed_group_width(V): the lanes that share a row, the power of two at or above V, 64 at most: the
+ * widths at which the kernels change form (and 64, beyond which a lane takes more than one element).
+ * pdt_relaxed_rows_per_block(V): rows served by one workgroup.  Both 0 for V < 1.
+ * ------------------------------------------------------------------------------------- */
+int pdt_relaxed_group_width(int64_t V);
+
+int pdt_relaxed_rows_per_block(int64_t V);
+
+int pdt_relaxed_gumbel(int op, int dtype, const void *param, int64_t B, int64_t p_sr, int64_t p_sv,
+                       const void *in1, const void *in2, int64_t R, int64_t V, void *out, void *stream);
+
+int pdt_relaxed_bernoulli(int op, int dtype, const void *param, int64_t B, int64_t p_sr, int64_t p_sv,
+                          const void *in1, const void *in2, int64_t R, int64_t V, void *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,9 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # because tests/test_random_walk_cpu.py pinned that number; a library built before them is still refused by
 # lib(), with its missing-entry-point message in place of the version one.  13: pdt_pad_variable_backward takes
 # the gradient's dtype (a library of version 12 would read the arguments one place off).  14: the attention
-# entry points' lse holds two numbers per row, (2, R) (a library of version 13 wrote and read R).
+# entry points' lse holds two numbers per row, (2, R) (a library of version 13 wrote and read R).  The relaxed-
+# sampling entry points were added at 14 in the way of the first exception (the same test file pins 14 now; no
+# existing declaration changed).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -222,6 +224,10 @@ SIGNATURES = {
     "pdt_binomial_coefficient": (_INT, [_P, _P, _I64, _P, _P, _P, _P]),
     "pdt_enumerate_cardinality": (_INT, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _INT, _P, _P]),
     "pdt_srswor": (_INT, [_P, _P, _P, _I64, _I64, _P, _P]),
+    "pdt_relaxed_group_width": (_INT, [_I64]),
+    "pdt_relaxed_rows_per_block": (_INT, [_I64]),
+    "pdt_relaxed_gumbel": (_INT, [_INT, _INT, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
+    "pdt_relaxed_bernoulli": (_INT, [_INT, _INT, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
     "pdt_ctc_prefix_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "pdt_ctc_prefix_search_plan": (_INT, [_I64, _I64, _P]),
     "pdt_ctc_prefix_search": (

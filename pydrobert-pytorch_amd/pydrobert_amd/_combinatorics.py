@@ -6,14 +6,18 @@ given cardinality unranks each row in the combinatorial number system, so the ``
 enumeration are never formed; the sampler is one launch over explicit uniforms.  CPU tensors, and the
 ``device="cpu"`` default of the enumerations, take torch bodies written from the same formulas.
 """
-from typing import Any, Optional, Tuple
+from typing import Any, Optional, Tuple, Union
 
 import torch
+from torch.distributions import constraints
+from torch.distributions.utils import lazy_property
 from torch.library import custom_op
 
-from . import _cabi
+from . import _cabi, argcheck
 
 __all__ = [
+    "BinaryCardinalityConstraint",
+    "SimpleRandomSamplingWithoutReplacement",
     "binomial_coefficient",
     "enumerate_binary_sequences",
     "enumerate_binary_sequences_with_cardinality",
@@ -317,3 +321,163 @@ def simple_random_sampling_without_replacement(
     u = torch.rand((total.numel(), out_size), device=device, dtype=torch.float32)
     b = torch.ops.pydrobert_amd.srswor(total, given, u)
     return b.view(total.shape + (out_size,)).to(torch.get_default_dtype())
+
+
+def _nonnegative_tensor(val: Any, name: str) -> torch.Tensor:
+    if not isinstance(val, torch.Tensor):
+        raise ValueError("{} is not a tensor".format(name))
+    if (val < 0).any():
+        raise ValueError("{} must be non-negative".format(name))
+    return val
+
+
+class BinaryCardinalityConstraint(constraints.Constraint):
+    """A binary vector that sums to ``given_count`` and is zero from ``total_count`` on (reference
+    _combinatorics.py:88-119)."""
+
+    is_discrete = True
+    event_dim = 1
+
+    def __init__(self, given_count: torch.Tensor, tmax: int, total_count: Optional[torch.Tensor] = None) -> None:
+        tmax = argcheck.is_posi(tmax, "tmax")
+        given_count = _nonnegative_tensor(given_count, "given_count")
+        if total_count is None:
+            beyond = torch.zeros(1, dtype=torch.bool, device=given_count.device)
+        else:
+            total_count = _nonnegative_tensor(total_count, "total_count")
+            beyond = total_count.unsqueeze(-1) <= torch.arange(tmax, device=total_count.device)
+        super().__init__()
+        self.given_count, self.total_count_mask = given_count, beyond
+
+    def check(self, value: torch.Tensor) -> torch.Tensor:
+        binary = ((value == 0) | (value == 1)).all(-1)
+        tail_empty = (self.total_count_mask.expand_as(value) * value).sum(-1) == 0
+        total = value.sum(-1)
+        return binary & tail_empty & (total == self.given_count.expand_as(total))
+
+
+class SimpleRandomSamplingWithoutReplacement(torch.distributions.ExponentialFamily):
+    r"""Binary vectors of ``out_size`` elements, uniform among those whose first ``total_count`` elements sum to
+    ``given_count`` and whose others are zero (reference _combinatorics.py:415-598): SRSWOR,
+    :math:`P(b | L) = I[\sum_t b_t = L] / \binom{T}{L}`, a special case of the conditional Bernoulli [chen1994]
+    and an exponential family.
+
+    ``total_count`` (:math:`T`) and ``given_count`` (:math:`L \le T`) broadcast to the batch shape;
+    ``out_size`` is at least ``total_count.max()``, its default.  :func:`sample` is one launch of the
+    sequential draw (:func:`simple_random_sampling_without_replacement`); the support is enumerated by
+    unranking, and only when every batch element has the same counts.
+    """
+
+    arg_constraints = {
+        "total_count": constraints.nonnegative_integer,
+        "given_count": constraints.nonnegative_integer,
+    }
+    _mean_carrier_measure = 0
+
+    def __init__(
+        self,
+        given_count: Union[int, torch.Tensor],
+        total_count: Union[int, torch.Tensor],
+        out_size: Optional[int] = None,
+        validate_args: Optional[bool] = None,
+    ):
+        device = None
+        if isinstance(given_count, torch.Tensor):
+            device = given_count.device
+            if isinstance(total_count, torch.Tensor) and given_count.device != total_count.device:
+                raise ValueError("given_count and total_count must be on the same device")
+        elif isinstance(total_count, torch.Tensor):
+            device = total_count.device
+        given_count = torch.as_tensor(given_count, device=device)
+        total_count = torch.as_tensor(total_count, device=device)
+        if out_size is None:
+            out_size = int(total_count.max().item())
+        given_count, total_count = torch.broadcast_tensors(given_count, total_count)
+        self.total_count, self.given_count = total_count, given_count
+        super().__init__(given_count.size(), torch.Size([out_size]), validate_args)
+        if self._validate_args:
+            _nonnegative_tensor(given_count, "given_count")
+            _nonnegative_tensor(total_count, "total_count")
+            if (given_count > total_count).any():
+                raise ValueError("given_count must be less than or equal to total_count")
+            if (total_count > out_size).any():
+                raise ValueError("out_size must be greater than or equal to total_count")
+
+    @constraints.dependent_property
+    def support(self):
+        return BinaryCardinalityConstraint(self.given_count, self.event_shape[0], self.total_count)
+
+    @property
+    def has_enumerate_support(self) -> bool:
+        total, given = self.total_count.flatten(), self.given_count.flatten()
+        return bool(((total == total[0]).all() & (given == given[0]).all()).item())
+
+    def enumerate_support(self, expand=True) -> torch.Tensor:
+        if not self.has_enumerate_support:
+            raise NotImplementedError(
+                "total_count must all be equal and given_count must all be equal to enumerate support"
+            )
+        total = int(self.total_count.flatten()[0].item())
+        given = int(self.given_count.flatten()[0].item())
+        support = enumerate_binary_sequences_with_cardinality(total, given, self.total_count.device, dtype=torch.float)
+        out_size = self.event_shape[0]
+        if out_size != total:
+            support = torch.nn.functional.pad(support, (0, out_size - total))
+        support = support.view((-1,) + (1,) * len(self.batch_shape) + (out_size,))
+        if expand:
+            support = support.expand((-1,) + self.batch_shape + (out_size,))
+        return support
+
+    @lazy_property
+    def log_partition(self) -> torch.Tensor:
+        """``log C(total_count, given_count)`` from a running sum of logs, in float32 as the reference's."""
+        log_factorial = torch.arange(
+            1, self.event_shape[0] + 1, device=self.total_count.device, dtype=torch.float
+        ).log().cumsum(0)  # fmt: skip
+        total, given = self.total_count.long(), self.given_count.long()
+        t, g, d = ((x - 1).clamp_min(0) for x in (total, given, total - given))
+        return log_factorial[t] - log_factorial[g] - log_factorial[d]
+
+    @property
+    def mean(self):
+        beyond = self.total_count.unsqueeze(-1) <= torch.arange(self.event_shape[0], device=self.total_count.device)
+        rate = (self.given_count / self.total_count.clamp_min(1.0)).unsqueeze(-1)
+        return rate.expand(self.batch_shape + self.event_shape).masked_fill(beyond, 0.0)
+
+    @property
+    def variance(self):
+        return self.mean * (1 - self.mean)
+
+    @property
+    def _natural_params(self):
+        return self.total_count.new_zeros(self.batch_shape + self.event_shape)
+
+    def _log_normalizer(self, logits):
+        if (logits == 0).all():
+            raise RuntimeError("Logits invalid")
+        return self.log_partition
+
+    def expand(self, batch_shape, _instance=None):
+        new = self._get_checked_instance(SimpleRandomSamplingWithoutReplacement, _instance)
+        batch_shape = list(batch_shape)
+        new.given_count = self.given_count.expand(batch_shape)
+        new.total_count = self.total_count.expand(batch_shape)
+        if "log_partition" in self.__dict__:
+            new.log_partition = self.log_partition.expand(batch_shape)
+        super(SimpleRandomSamplingWithoutReplacement, new).__init__(
+            torch.Size(batch_shape), self.event_shape, validate_args=False
+        )
+        new._validate_args = self._validate_args
+        return new
+
+    def sample(self, sample_shape=torch.Size([])):
+        shape = self._extended_shape(torch.Size(sample_shape))
+        with torch.no_grad():
+            return simple_random_sampling_without_replacement(
+                self.total_count.expand(shape[:-1]), self.given_count.expand(shape[:-1]), self.event_shape[0]
+            )
+
+    def log_prob(self, value):
+        if self._validate_args:
+            self._validate_sample(value)
+        return (-self.log_partition).expand(value.shape[:-1])

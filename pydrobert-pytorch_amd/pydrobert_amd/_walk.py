@@ -1,17 +1,21 @@
 """Sampling from language models on MI355X (``csrc/random_walk.hip``): ``random_walk_advance`` and
 ``RandomWalk``.
 """
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Tuple, Union
 
 import torch
+from torch.distributions import constraints
 from torch.library import custom_op, register_autograd
 
 from . import _cabi, argcheck, switches
+from ._combinatorics import enumerate_vocab_sequences
 from ._decoding import _dense_table
 from ._lm import LookupLanguageModel
+from ._seqops import SequenceLogProbabilities
 from ._step import _f32, _i64
+from ._string import fill_after_eos
 
-__all__ = ["RandomWalk", "random_walk_advance"]
+__all__ = ["RandomWalk", "SequentialLanguageModelDistribution", "TokenSequenceConstraint", "random_walk_advance"]
 
 
 _WALK_INVALID, _WALK_REACH, _WALK_BAD_LENS = 2, 4, 8
@@ -447,3 +451,186 @@ class RandomWalk(torch.nn.Module):
                     y_lens = y_lens + 1
             T = t + 1
         return y[:T], y_lens, log_probs.to(torch.promote_types(out_dtype, log_probs.dtype))
+
+
+class TokenSequenceConstraint(constraints.Constraint):
+    """Completed token sequences (reference _decoding.py:1724-1770): vectors of integers in ``[0, vocab_size)``
+    that either have ``max_iters`` elements, or have at most that many (any number when unset) and contain
+    ``eos``.  Whatever follows the first ``eos`` of a sequence is ignored."""
+
+    vocab_size: int
+    eos: Optional[int]
+    max_iters: Union[int, float]
+    is_discrete = True
+    event_dim = 1
+
+    def __init__(self, vocab_size: int, eos: Optional[int] = None, max_iters: Optional[int] = None) -> None:
+        vocab_size = argcheck.is_posi(vocab_size, "vocab_size")
+        if eos is None and max_iters is None:
+            raise ValueError("At least one of max_iters or eos must be non-none")
+        eos = argcheck.is_int(eos, "eos", True)
+        max_iters = argcheck.is_nonnegi(max_iters, "max_iters", True)
+        super().__init__()
+        self.vocab_size, self.eos = vocab_size, eos
+        self.max_iters = float("inf") if max_iters is None else max_iters
+
+    def check(self, value: torch.Tensor):
+        completed = value.size(-1) == self.max_iters
+        if self.eos is not None:
+            if value.device.type == "cuda":
+                value = fill_after_eos(value, self.eos, -1)
+            else:  # (the kernel's rule in torch ops: constraints are checked on the CPU too)
+                is_eos = value == self.eos
+                value = value.masked_fill((is_eos.cumsum(-1) - is_eos.long()) > 0, self.eos)
+            completed = (value == self.eos).any(-1) & (value.size(-1) <= self.max_iters) | completed
+        in_vocab = ((value % 1 == 0) & (value >= 0) & (value < self.vocab_size)).all(-1)
+        return in_vocab & completed
+
+
+class SequentialLanguageModelDistribution(torch.distributions.distribution.Distribution):
+    """A :class:`RandomWalk` over a :class:`SequentialLanguageModel` as a ``Distribution`` (reference
+    _decoding.py:1773-2029), the object the sequence-level estimators are written against.
+
+    :func:`sample` runs the walk; :func:`log_prob` runs the model over the given sequences and
+    :class:`SequenceLogProbabilities`; :func:`enumerate_support` (``max_iters`` set) lists every sequence, with
+    those that agree up to their first ``eos`` merged.  All three run on this package's kernels.
+
+    Two batching modes.  With ``batch_size`` unset the samples themselves are the model's batch:
+    ``sample()`` is ``(T,)`` and ``sample([M])`` is ``(M, T)``, drawn in one walk.  With ``batch_size = N`` (a
+    model conditioned on N inputs through ``initial_state``) ``sample()`` is ``(N, T)`` and ``sample([M])`` is
+    ``(M, N, T)``: M walks of batch N one after the other, stacked, and padded with ``eos`` to one length.
+
+    ``cache_samples`` keeps the last samples with their log probabilities, so that a :func:`log_prob` of the
+    value just drawn costs a comparison, until :func:`clear_cache` or the next value.  As in the reference, the
+    log probabilities are those of the default ``update_log_probs_for_step``; a subclassed walk's adjusted ones
+    are what :func:`sample` caches.
+    """
+
+    arg_constraints = dict()
+
+    def __init__(
+        self,
+        random_walk: RandomWalk,
+        batch_size: Optional[int] = None,
+        initial_state: Optional[Dict[str, torch.Tensor]] = None,
+        max_iters: Optional[int] = None,
+        cache_samples: bool = False,
+        validate_args: Optional[bool] = None,
+    ):
+        if batch_size is None:
+            batch_shape = torch.Size([])
+        else:
+            batch_shape = torch.Size([argcheck.is_posi(batch_size, "batch_size")])
+        if max_iters is None:
+            if random_walk.eos is None:
+                raise ValueError("random_walk.eos must be set if max_iters isn't")
+            event_shape = torch.Size([1])
+        else:
+            max_iters = argcheck.is_nonnegi(max_iters, "max_iters")
+            event_shape = torch.Size([max_iters])
+        cache_samples = argcheck.is_bool(cache_samples, "cache_samples")
+        validate_args = argcheck.is_bool(validate_args, "validate_args", True)
+        self.random_walk = random_walk
+        super().__init__(batch_shape, event_shape, validate_args)
+        self.initial_state = dict() if initial_state is None else initial_state
+        self.cache_samples, self.max_iters = cache_samples, max_iters
+        self._samples_cache: Optional[torch.Tensor] = None
+        self._log_probs_cache: Optional[torch.Tensor] = None
+        if self._validate_args and not all(
+            isinstance(k, str) and isinstance(v, torch.Tensor) for k, v in self.initial_state.items()
+        ):
+            raise ValueError("initial_state is not a dictionary of str:Tensor")
+
+    def _validate_sample(self, value: torch.Tensor):
+        # (the event dimension is as long as the walk was; its length is the support's to check)
+        exp_shape, act_shape = tuple(self.batch_shape + self.event_shape), tuple(value.shape)
+        try:
+            torch.broadcast_shapes(exp_shape, act_shape)
+        except RuntimeError:
+            raise ValueError(
+                "value of shape {} cannot broadcast with batch_shape+event_shape {}".format(act_shape, exp_shape)
+            )
+        ok = self.support.check(value)
+        if not ok.all():
+            raise ValueError("value of shape {} has values outside of the support: {}".format(act_shape, ok))
+
+    @constraints.dependent_property
+    def support(self):
+        return TokenSequenceConstraint(self.random_walk.lm.vocab_size, self.random_walk.eos, self.max_iters)
+
+    def sample(self, sample_shape: torch.Size = torch.Size([])) -> torch.Tensor:
+        shape = list(self._extended_shape(sample_shape))
+        num_samples = 1
+        for d in sample_shape:
+            num_samples *= d
+        walk = self.random_walk
+        if num_samples == 0:
+            return torch.empty(shape, device=walk.device_buffer.device)
+        if len(self.batch_shape):
+            drawn = [walk(self.initial_state.copy(), self.batch_shape[0], self.max_iters) for _ in range(num_samples)]
+            log_probs = torch.stack([d[2] for d in drawn])
+            if walk.eos is None:  # (every walk took max_iters steps)
+                samples = torch.stack([d[0].T for d in drawn])
+            else:  # walks of different lengths: padded with eos to the longest
+                samples = torch.nn.utils.rnn.pad_sequence([d[0] for d in drawn], padding_value=walk.eos)
+                samples = samples.flatten(1).T
+        else:
+            samples, _, log_probs = walk(self.initial_state.copy(), num_samples, self.max_iters)
+            samples = samples.T
+        shape[-1] = samples.size(-1)
+        samples = samples.reshape(shape)
+        if self.cache_samples:
+            self._samples_cache = samples
+            self._log_probs_cache = log_probs.view(shape[:-1])
+        return samples
+
+    @property
+    def has_enumerate_support(self) -> bool:
+        return self.max_iters is not None
+
+    def enumerate_support(self, expand=True) -> torch.Tensor:
+        if not self.has_enumerate_support:
+            raise NotImplementedError("random_walk.max_iters must be set in order to enumerate support")
+        walk = self.random_walk
+        support = enumerate_vocab_sequences(self.max_iters, walk.lm.vocab_size, walk.device_buffer.device)
+        if walk.eos is not None:
+            support = torch.unique(fill_after_eos(support, walk.eos, 1), dim=0)
+        if len(self.batch_shape):
+            support = support.view((-1,) + (1,) * len(self.batch_shape) + support.shape[-1:])
+            if expand:
+                support = support.expand((-1,) + self.batch_shape + support.shape[-1:])
+        return support
+
+    def clear_cache(self):
+        """Forget the cached samples and their log probabilities."""
+        self._samples_cache = self._log_probs_cache = None
+
+    def log_prob(self, value: torch.Tensor) -> torch.Tensor:
+        if self._validate_args:
+            self._validate_sample(value)
+        batch_size = self.batch_shape[0] if len(self.batch_shape) else 1
+        num_samples = value.numel() // (batch_size * value.size(-1))
+        shape = value.shape[:-1]
+        if num_samples == 0:
+            return torch.empty(shape, device=value.device)
+        if (
+            self.cache_samples
+            and self._samples_cache is not None
+            and self._samples_cache.shape == value.shape
+            and (self._samples_cache == value).all()
+        ):
+            assert self._log_probs_cache is not None
+            return self._log_probs_cache
+        if self.cache_samples:
+            self._samples_cache = value
+        lm = self.random_walk.lm
+        if len(self.batch_shape):  # one call of the model per sample, each over the batch
+            value = value.reshape((-1,) + value.shape[-2:]).transpose(1, 2)
+            log_probs = torch.stack([lm(hist[:-1].long(), self.initial_state.copy()) for hist in value])
+        else:  # every sample in one batch
+            value = value.reshape(-1, value.size(-1))
+            log_probs = lm(value.T[:-1].long(), self.initial_state.copy()).transpose(0, 1)
+        log_probs = SequenceLogProbabilities(1, self.random_walk.eos)(log_probs, value.long()).view(shape)
+        if self.cache_samples:
+            self._log_probs_cache = log_probs
+        return log_probs

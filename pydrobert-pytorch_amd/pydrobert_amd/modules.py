@@ -22,6 +22,7 @@ from ._pad import ChunkBySlices, PadMaskedSequence, PadVariable
 from ._seqops import CTCGreedySearch, SequenceLogProbabilities
 from ._walk import RandomWalk
 from ._rl import TimeDistributedReturn
+from ._relaxed import GumbelOneHotCategoricalRebarControlVariate, LogisticBernoulliRebarControlVariate
 from ._lm import (
     ExtractableSequentialLanguageModel,
     ExtractableShallowFusionLanguageModel,
@@ -65,6 +66,8 @@ __all__ = [
     "RandomWalk",
     "SequenceLogProbabilities",
     "TimeDistributedReturn",
+    "GumbelOneHotCategoricalRebarControlVariate",
+    "LogisticBernoulliRebarControlVariate",
     "HardOptimalCompletionDistillationLoss",
     "MinimumErrorRateLoss",
     "BeamSearch",

@@ -905,6 +905,51 @@ int pdt_relaxed_gumbel(int op, int dtype, const void *param, int64_t B, int64_t 
 int pdt_relaxed_bernoulli(int op, int dtype, const void *param, int64_t B, int64_t p_sr, int64_t p_sv,
                           const void *in1, const void *in2, int64_t R, int64_t V, void *out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Sample-axis reductions of the Monte Carlo estimators (reference _mc.py:145-173, 230-233, 297-301,
+ * 390-404, 530-564; _enumerate_estimator.py:68-77): the whole formula of a column in one launch, its
+ * backward in one elementwise launch.  dtype 0 float32, 1 float64.  Data are (M, B), M >= 1 samples of
+ * B columns.  in[6] are f, a, cz, c, lp, lq in that order, null where absent; strides[12] their element
+ * strides (s_m, s_b), pair by pair (0 is allowed: c is (B,), s_m = 0).  out is (B,) dense; stats is
+ * (5, B) float64, written by the forward and read by the backward (max, arg-max, mean or normaliser).
+ *   kind 0  MEAN      f                 mean_m f;  is_log: logsumexp_m f - log M
+ *   kind 1  SCORE     f [a [cz | c]] lp mean_m(f - a + c + cz);  is_log: with x = clamp(max_m f, lowest / 2,
+ *                                       max / 2) and e(t) = exp(clamp(t - x, EPS_NINF, EPS_INF)):
+ *                                       log(max(mean_m(e(f) - e(a) + e(c) + e(cz)), exp(EPS_NINF))) + x.
+ *                                       lp does not enter the value; its gradient is the REINFORCE weight
+ *                                       g (f - a + c) / M (is_log: the e() terms, over the floored mean)
+ *   kind 2  WEIGHTED  f lp [lq]         sum_m f exp(l);  is_log: logsumexp_m(f + l);  l = lp - lq - kappa,
+ *                                       mode 0 kappa = log M, 1 l = log_softmax_m(lp - lq), 2 l = lp (no lq)
+ * pdt_mc_reduce_backward: g is (B,) dense; grads[6] are dense (M, B) (grads[3], of c: (B,)), null where
+ * not wanted.  The clamps pass the gradient on their bounds; the path through the column maximum goes to
+ * the index the forward selected (the lowest of equals).  grads[5] (lq) is written with zeros.
+ * PDT_E_ARG: an unknown kind / mode / dtype, M < 1, B < 0, a missing f / lp / stats / out / g, an input
+ * that the kind does not take, a gradient asked for an absent input.  B == 0 is OK (nothing to do).
+ * pdt_mc_reduce_plan: the form that serves (M, B) with f read through (s_m, s_b): 0 lane = column,
+ * 1 one wave per column (M >= 64, and B < 16384 or m the denser axis).  -1 for M < 1 or B < 1.
+ * ------------------------------------------------------------------------------------- */
+int pdt_mc_reduce_plan(int64_t M, int64_t B, int64_t s_m, int64_t s_b);
+
+int pdt_mc_reduce(int kind, int is_log, int mode, int dtype, int64_t M, int64_t B, const void *const *in,
+                  const int64_t *strides, void *out, double *stats, void *stream);
+
+int pdt_mc_reduce_backward(int kind, int is_log, int mode, int dtype, int64_t M, int64_t B,
+                           const void *const *in, const int64_t *strides, const void *g, const double *stats,
+                           void *const *grads, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The accept / reject scan of independent Metropolis-Hastings (reference _mc.py:715-733), one lane per
+ * batch column.  dtype 0 float32, 1 float64.  ratio (M, B) through (r_sm, r_sb) is log P - log Q of the
+ * M proposals, ratio0 (B,) through r0_s that of the sample carried in, log_u (M, B) through (u_sm, u_sb).
+ * Per column, last = ratio0, cur = -1; for n = 0 .. M - 1: if (ratio[n] - last) > log_u[n] then
+ * last = ratio[n], cur = n; idx[n] = cur.  idx is (M, B) int32 dense, last (B,), last_idx (B,) int32 the
+ * final cur.  A NaN rejects; a rejected -inf leaves last as it was (selected, not blended).
+ * PDT_E_ARG: an unknown dtype, M < 0, B < 0, a null array that would be touched.  PDT_E_TOO_LONG: M >= 2^31.
+ * ------------------------------------------------------------------------------------- */
+int pdt_imh_chain(int dtype, const void *ratio, int64_t r_sm, int64_t r_sb, const void *ratio0, int64_t r0_s,
+                  const void *log_u, int64_t u_sm, int64_t u_sb, int64_t M, int64_t B, int32_t *idx, void *last,
+                  int32_t *last_idx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

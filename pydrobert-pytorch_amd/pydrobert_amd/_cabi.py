@@ -22,7 +22,7 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # the gradient's dtype (a library of version 12 would read the arguments one place off).  14: the attention
 # entry points' lse holds two numbers per row, (2, R) (a library of version 13 wrote and read R).  The relaxed-
 # sampling entry points were added at 14 in the way of the first exception (the same test file pins 14 now; no
-# existing declaration changed).
+# existing declaration changed), and so were those of the estimators (pdt_mc_reduce*, pdt_imh_chain).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -228,6 +228,10 @@ SIGNATURES = {
     "pdt_relaxed_rows_per_block": (_INT, [_I64]),
     "pdt_relaxed_gumbel": (_INT, [_INT, _INT, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
     "pdt_relaxed_bernoulli": (_INT, [_INT, _INT, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
+    "pdt_mc_reduce_plan": (_INT, [_I64, _I64, _I64, _I64]),
+    "pdt_mc_reduce": (_INT, [_INT, _INT, _INT, _INT, _I64, _I64, _P, _P, _P, _P, _P]),
+    "pdt_mc_reduce_backward": (_INT, [_INT, _INT, _INT, _INT, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "pdt_imh_chain": (_INT, [_INT, _P, _I64, _I64, _P, _I64, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "pdt_ctc_prefix_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
     "pdt_ctc_prefix_search_plan": (_INT, [_I64, _I64, _P]),
     "pdt_ctc_prefix_search": (

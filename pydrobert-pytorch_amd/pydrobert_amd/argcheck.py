@@ -82,3 +82,28 @@ def is_posf(val, name=None, allow_none=False):
 def is_closed01(val, name=None, allow_none=False):
     val = is_float(val, name, allow_none)
     return _num(val, name, allow_none, lambda v: 0.0 <= v <= 1.0, "in [0, 1]")
+
+
+def is_a(val, t, name=None, allow_none=False):
+    """``val`` is an instance of ``t`` (argcheck.py:289-296)."""
+    if allow_none and val is None:
+        return None
+    if not isinstance(val, t):
+        suf = "n" if t.__name__.startswith(("a", "e", "i", "o", "u")) else ""
+        raise ValueError("{} is not a{} {}".format(_nv(name, val), suf, t.__name__))
+    return val
+
+
+def is_lt(val, other, name=None, other_name=None, allow_none=False):
+    """``val < other``, elementwise for tensors (argcheck.py:431-445)."""
+    if allow_none and val is None:
+        return None
+    for v, n in ((val, name), (other, other_name)):
+        if not isinstance(v, (int, float, np.integer, np.floating, torch.Tensor)):
+            raise ValueError("{} is not num-like".format(_nv(n, v)))
+    val_ = torch.as_tensor(val)
+    other_ = torch.as_tensor(other, device=val_.device)
+    if (val_ >= other_).any():
+        x = "entirely " if val_.numel() > 1 else ""
+        raise ValueError("{} is not {}less than {}".format(_nv(name, val), x, _nv(other_name, other)))
+    return val

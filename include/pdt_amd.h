@@ -224,7 +224,7 @@ int pdt_ctc_lm_table_search(const float *logits, int64_t T, int64_t N, int64_t V
  *   workspace: pdt_ctc_prefix_search_workspace_bytes(T, N, V, width) bytes of scratch
  *          (the prefix trie: one (parent, token) record per frame and beam entry, the
  *          checkpoints of the output walk and, for rows beyond the LDS, the rows of the ring).
- *   width <= 32 (wider beams: one pdt_ctc_prefix_search_advance per frame).  S must be at least min(T, max lens): frames beyond S are not decoded.
+ *   width <= 32 (wider beams, up to 128 prefixes: pdt_ctc_prefix_search_wide below).  S must be at least min(T, max lens): frames beyond S are not decoded.
  *   Rows of up to 511 tokens and of 512 .. 16 447 tokens (contiguous logits) are held in the
  *   registers of the producer wave that reads them (ctc_search.hip / ctc_rowreg.hip); other rows
  *   of up to about 10 000 tokens live in LDS (one row of probabilities per slot of a three-slot
@@ -244,6 +244,28 @@ int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, 
                           int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
                           int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
                           void *workspace, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * The same search for beams the kernels above cannot hold: width <= 128, every frame in one launch
+ * (csrc/ctc_search_wide.hip: one workgroup of eight waves per utterance, the beam's state in LDS
+ * between frames, the workgroup selection of the plain step kernel; workgroups never wait on one
+ * another).  Arguments, outputs and status codes as pdt_ctc_prefix_search; narrower widths are
+ * accepted too and give the same beams (probabilities may differ in the last bits: merged masses
+ * are summed in index order here).  A frame with fewer than `width` candidates leaves the rest of
+ * the beam absent: probability -inf, length 0, a zero column of y.
+ *   workspace: pdt_ctc_prefix_search_wide_workspace_bytes(T, N, V, width) bytes -- the prefix trie,
+ *          the next-token tables of widths above 64 (8 width^2 bytes per utterance) and one row of
+ *          probabilities per utterance (read by rows of more than about 17 000 tokens, which do not
+ *          fit the LDS); 0 for arguments the search does not take.
+ *   PDT_E_TOO_LONG: width > 128, width * (V + 1) >= 2^31, and the index limits of
+ *          pdt_ctc_prefix_search.
+ * ------------------------------------------------------------------------------------- */
+int64_t pdt_ctc_prefix_search_wide_workspace_bytes(int64_t T, int64_t N, int64_t V, int64_t width);
+
+int pdt_ctc_prefix_search_wide(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                               int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
+                               int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
+                               void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * ctc_prefix_search_advance (reference _decoding.py:636-934): one CTC prefix-search step with

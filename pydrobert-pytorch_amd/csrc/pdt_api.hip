@@ -136,6 +136,8 @@ extern "C" {
 //     that the workspace it is given was filled by a call that keeps its tables (kept_tables below)
 //     and classifies for itself otherwise: the sequence pdt_lev, pdt_lev_classified of earlier
 //     callers keeps its results (the version stays 12)
+// 14, then additively: pdt_ctc_prefix_search_wide, pdt_ctc_prefix_search_wide_workspace_bytes (the
+//     one-launch CTC search for beams of up to 128 prefixes, csrc/ctc_search_wide.hip)
 int pdt_amd_abi_version(void) { return 14; }
 
 int pdt_amd_set_switch(const char *name, int value) {

@@ -238,6 +238,11 @@ SIGNATURES = {
         _INT,
         [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P],
     ),
+    "pdt_ctc_prefix_search_wide_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "pdt_ctc_prefix_search_wide": (
+        _INT,
+        [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P],
+    ),
 }
 
 _lib = None

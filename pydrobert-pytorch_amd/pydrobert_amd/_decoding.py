@@ -21,7 +21,8 @@ from ._step import _ctc_step_with_lm_scores, _f32, _i64, ctc_prefix_search_advan
 
 __all__ = ["BeamSearch", "CTCPrefixSearch", "ctc_prefix_search"]
 
-MAX_CTC_WIDTH = 32
+MAX_CTC_WIDTH = 128  # one launch: the wave-wide kernels up to MAX_CTC_WAVE_WIDTH, csrc/ctc_search_wide.hip beyond
+MAX_CTC_WAVE_WIDTH = 32
 
 
 @custom_op("pydrobert_amd::ctc_prefix_search", mutates_args=())
@@ -39,6 +40,7 @@ def _ctc_prefix_search_op(
         raise RuntimeError("width must be positive")
     if width > MAX_CTC_WIDTH:  # (CTCPrefixSearch / ctc_prefix_search run such beams frame by frame)
         raise RuntimeError("the one-kernel search holds at most {} prefixes".format(MAX_CTC_WIDTH))
+    wide = width > MAX_CTC_WAVE_WIDTH
     dtype = logits.dtype
     logits = _f32(logits)
     if lens is None:
@@ -56,16 +58,14 @@ def _ctc_prefix_search_op(
         y = torch.empty((S, N, width), device=device, dtype=torch.long)
         y_lens = torch.empty((N, width), device=device, dtype=torch.long)
         y_probs = torch.empty((N, width), device=device, dtype=torch.float)
-        ws = torch.empty(
-            (int(L.pdt_ctc_prefix_search_workspace_bytes(T, N, V, width)),),
-            device=device, dtype=torch.uint8,
-        )  # fmt: skip
-        rc = L.pdt_ctc_prefix_search(
+        ws_bytes = L.pdt_ctc_prefix_search_wide_workspace_bytes if wide else L.pdt_ctc_prefix_search_workspace_bytes
+        ws = torch.empty((int(ws_bytes(T, N, V, width)),), device=device, dtype=torch.uint8)
+        rc = (L.pdt_ctc_prefix_search_wide if wide else L.pdt_ctc_prefix_search)(
             _cabi.ptr(logits), T, N, V, logits.stride(0), logits.stride(1), logits.stride(2),
             _cabi.ptr(lens), int(width), S, _cabi.ptr(y), _cabi.ptr(y_lens), _cabi.ptr(y_probs),
             _cabi.ptr(ws), _cabi.stream_ptr(device),
         )  # fmt: skip
-    _cabi.check(rc, "pdt_ctc_prefix_search")
+    _cabi.check(rc, "pdt_ctc_prefix_search_wide" if wide else "pdt_ctc_prefix_search")
     return y, y_lens, y_probs.to(dtype)
 
 
@@ -92,7 +92,7 @@ def ctc_prefix_search(
     route of :class:`CTCPrefixSearch` instead (same beams, differentiable probabilities).
     """
     if torch.jit.is_scripting() or not (
-        width > 32 or (torch.is_grad_enabled() and logits.requires_grad)  # (32: MAX_CTC_WIDTH)
+        width > 128 or (torch.is_grad_enabled() and logits.requires_grad)  # (128: MAX_CTC_WIDTH)
     ):
         return torch.ops.pydrobert_amd.ctc_prefix_search(logits, width, lens)
     return CTCPrefixSearch(width)(logits, lens)
@@ -151,9 +151,9 @@ class CTCPrefixSearch(torch.nn.Module):
         # caller wants gradients with respect to the logits (the reference's probabilities are
         # differentiable, _decoding.py:1093, :1188), the search runs frame by frame instead: every
         # frame is one kernel whose masses carry an autograd formula.
-        # Beams wider than the one-kernel search holds (32 prefixes) also go frame by frame, on the
+        # Beams wider than the one-kernel search holds (128 prefixes) also go frame by frame, on the
         # plain step kernel (csrc/advance_wide.hip).
-        stepwise = (torch.is_grad_enabled() and logits.requires_grad) or self.width > 32  # (MAX_CTC_WIDTH; TorchScript takes no globals)
+        stepwise = (torch.is_grad_enabled() and logits.requires_grad) or self.width > 128  # (MAX_CTC_WIDTH; TorchScript takes no globals)
         prev: Dict[str, torch.Tensor] = dict()
         if initial_state is not None:
             prev = initial_state

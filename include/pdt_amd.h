@@ -200,11 +200,19 @@ int pdt_ocd_loss_backward(const float *logits, int64_t H, int64_t N, int64_t V, 
  *     (a bigram model: ctx_mod = 1, the row is the last token; a trigram model over U context symbols:
  *     ctx_base = ctx_mod = U, U^2 rows -- 4 GB at U = 1001, V = 1000: sized for this card's HBM, built once
  *     per model by the model's own scoring kernel over every context).
- *     width <= 32, V <= 5119.  workspace: pdt_ctc_lm_table_search_workspace_bytes (trie + checkpoints).
+ *     width <= 32, V <= 5119.  workspace: pdt_ctc_lm_table_search_workspace_bytes (trie + checkpoints),
+ *     0 for sizes the search does not take.
+ *   pdt_ctc_lm_table_search_plan (host only, no device work): what the launch decides from the sizes --
+ *     plan6 = {checkpoint shift, checkpoints per utterance, 64-token chunks per row of the kernel instance
+ *     (8 / 16 / 32 / 48 / 80), 16 for the instance with the width as a constant else 0, bytes of the row
+ *     ring, LDS bytes per workgroup}.  Returns PDT_OK or the code pdt_ctc_lm_table_search returns for
+ *     (T, V, width).  Checkpoints lie 2^shift frames apart: the shift is the smallest >= 5 at which the
+ *     (T / 2^shift + 1) x width table of the output walk fits the row ring.
  * ------------------------------------------------------------------------------------- */
 int pdt_lm_factor_table(const float *lm_log_probs, int64_t rows, int64_t V, float beta, int valid_mixture,
                         float *out, int64_t out_stride, void *stream);
 int64_t pdt_ctc_lm_table_search_workspace_bytes(int64_t T, int64_t N, int64_t V, int64_t width);
+int pdt_ctc_lm_table_search_plan(int64_t T, int64_t V, int64_t width, int32_t *plan6);
 int pdt_ctc_lm_table_search(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st, int64_t lg_sn,
                             int64_t lg_sv, const int64_t *lens, int64_t width, int64_t S, const float *factors,
                             const float *factor_max, int64_t contexts, int64_t f_stride, int64_t sos_row,
@@ -387,14 +395,18 @@ int pdt_beam_search_table_paths(const uint32_t *trie, const int32_t *finish, int
  *   its beam from frame frame_lens[n] on (:1165-1181).
  *   Histories are not copied from frame to frame: every batch element has 2 * width history slots;
  *   a prefix that survives a frame keeps its slot, an extended prefix gets a free slot, a copy of its
- *   source's tokens and the new token (int16 tokens when V <= 32767, int64 otherwise).
+ *   source's tokens and the new token (int16 tokens).
  *   Outputs, contiguous: y (n_frames, N, width) int64, zero beyond an entry's length and for absent
  *   entries; y_lens (N, width) int64; nb, b (N, width) float32 -- the two masses of every entry (the
  *   module returns nb + b).  Same bits as pdt_lookup_lm_log_probs -> pdt_fusion_ext ->
  *   pdt_ctc_prefix_search_advance frame after frame.
  *   workspace: pdt_ctc_lookup_lm_search_workspace_bytes(n_frames, N, V, width, max_ngram, U) bytes.
  * width <= 32; max_ngram <= 16.
+ *   pdt_ctc_lookup_lm_search_lds_bytes (host only, no device work): the dynamic LDS of the launch for
+ *   (V, width), 0 when the shape does not fit -- pdt_ctc_lookup_lm_search then returns PDT_E_TOO_LONG.
+ *   A workgroup holds two rows of V floats at the least, so no V above 20 480 fits at any width.
  * ------------------------------------------------------------------------------------- */
+int64_t pdt_ctc_lookup_lm_search_lds_bytes(int64_t V, int64_t width);
 int64_t pdt_ctc_lookup_lm_search_workspace_bytes(int64_t n_frames, int64_t N, int64_t V, int64_t width,
                                                  int64_t max_ngram, int64_t U);
 int pdt_ctc_lookup_lm_search(

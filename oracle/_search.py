@@ -214,6 +214,19 @@ def ctc_prefix_search_lm(logits, width, lens=None, lm=None, beta=0.2, valid_mixt
         y_new, last_new, lens_new, (nb_new, b_new), isp_new, src, kept = ctc_prefix_search_advance(
             (np.ascontiguousarray(ext, dtype=f32), nonext, blank), W, (nb, b), y, y_last, y_lens, isp
         )
+        # A beam wider than the candidates that exist (width > K' * (V + 1)) is filled up with candidates of
+        # mass -inf: absent entries, and once such an entry is a source, its extensions (b = -inf * 0 = NaN)
+        # and the extensions that were merged into a longer prefix (nb = -inf).  The reference keeps them as
+        # prefixes: after two such frames in a row (width > (V + 1)^2) every probability it returns is NaN.
+        # Here they stay what they are -- absent: no mass, no tokens, prefix of nothing -- so the search is
+        # defined for those beams too (brute force over the alignments while every prefix fits the beam:
+        # tests/test_lm_search_forms_gpu.py).  No entry of any other beam has a total of -inf.
+        with np.errstate(invalid="ignore"):
+            gone = ~((nb_new + b_new) > NINF)  # (N, W): -inf or NaN
+        if gone.any():
+            nb_new, b_new = np.where(gone, f32(NINF), nb_new), np.where(gone, f32(NINF), b_new)
+            y_new, last_new, lens_new = np.where(gone[None], 0, y_new), np.where(gone, 0, last_new), np.where(gone, 0, lens_new)
+            isp_new = isp_new & ~gone[:, :, None] & ~gone[:, None, :]
         if fuse:  # :1154-1163
             flat = (np.arange(0, Kp * N, Kp)[:, None] + src).reshape(-1)
             prev = lm.mix_by_mask(lm.extract_by_src(prev, flat), lm.extract_by_src(in_next, flat), kept.reshape(-1))

@@ -132,7 +132,8 @@ __device__ __forceinline__ void lm_score_row(const LmTrie &a, const int (&ct)[kL
   wave_sync();
 }
 
-// HT: the element type of the history slots -- int16_t when every token fits (V <= 32767), else int64_t
+// HT: the element type of the history slots -- int16_t: every token fits, the LDS plan admits no
+// vocabulary above 20 480 tokens (pdt_ctc_lookup_lm_search_lds_bytes)
 template <typename HT>
 __device__ __forceinline__ void lm_frame(const CtcLmAdvArgs &A, unsigned char *smem) {
   const CtcAdvArgs &a = A.s;
@@ -514,10 +515,22 @@ extern "C" int pdt_debug_lm_stamps(unsigned long long *out, int reset) {
 }
 #endif
 
+// The dynamic LDS of the search for (V, width), 0 when the shape does not fit (host arithmetic only: what
+// pdt_ctc_lookup_lm_search decides before it launches).  A workgroup's LDS holds two rows of V floats at
+// the least -- 8 V bytes of the 160 KB -- so no vocabulary above 20 480 tokens fits, whatever the width:
+// the histories are 16-bit tokens throughout (V <= 32 767 would do).
+extern "C" int64_t pdt_ctc_lookup_lm_search_lds_bytes(int64_t V, int64_t width) {
+  using namespace pdt;
+  if (V < 1 || width < 1 || V > 32767 || width > kMaxWidth) return 0;
+  CtcLmAdvArgs A{};
+  A.s.V = (int)V; A.s.W = (int)width; A.s.Kp = (int)width;
+  return (int64_t)plan_lm_frame(A);
+}
+
 extern "C" int64_t pdt_ctc_lookup_lm_search_workspace_bytes(int64_t n_frames, int64_t N, int64_t V, int64_t width,
                                                             int64_t max_ngram, int64_t U) {
   if (n_frames < 0 || N < 0 || V < 1 || width < 1 || U < V + 1) return 0;
-  return (int64_t)pdt::plan_lm_search(n_frames, N, width, V <= 32767 ? 2 : 8).total;
+  return (int64_t)pdt::plan_lm_search(n_frames, N, width, 2).total;
 }
 
 extern "C" int pdt_ctc_lookup_lm_search(
@@ -534,8 +547,8 @@ extern "C" int pdt_ctc_lookup_lm_search(
     return PDT_E_ARG;
   if (V >= (1 << 30) || n_frames >= (1 << 26) || N >= (1ll << 31)) return PDT_E_TOO_LONG;
   if (width > kMaxWidth || max_ngram > kLmMaxOrder) return PDT_E_TOO_LONG;
-  const int hb = V <= 32767 ? 2 : 8;
-  const LmSearchPlan p = plan_lm_search(n_frames, N, width, hb);
+  if (V > 32767) return PDT_E_TOO_LONG;  // (16-bit histories; the LDS plan below admits no such row anyway)
+  const LmSearchPlan p = plan_lm_search(n_frames, N, width, 2);
   if ((int64_t)p.total > workspace_bytes) return PDT_E_ARG;
   unsigned char *w = reinterpret_cast<unsigned char *>(workspace);
   LmSearchState st[2];
@@ -566,20 +579,15 @@ extern "C" int pdt_ctc_lookup_lm_search(
   a.Kp = (int)width;  // (the LDS plan of the widest frame; the first frame's single prefix fits inside it)
   const size_t smem = plan_lm_frame(A);
   if (smem == 0) return PDT_E_TOO_LONG;
-  auto kern = hb == 2 ? ctc_lm_search_kernel<int16_t> : ctc_lm_search_kernel<int64_t>;
+  auto kern = ctc_lm_search_kernel<int16_t>;
   if (const int rc = set_lds(kern, smem)) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)N), dim3(64 * a.waves_per_wg), smem, hs, A, st[0], st[1], probs, p_st,
                      p_sn, p_sv, (int)n_frames);
   const int rc = (int)hipGetLastError();
   if (rc != PDT_OK) return rc;
   const LmSearchState &fin = st[n_frames & 1];
-  if (hb == 2)
-    hipLaunchKernelGGL(lm_search_gather_kernel<int16_t>, dim3((unsigned)N), dim3(256), 0, hs,
-                       reinterpret_cast<const int16_t *>(w + p.hist), 2 * width * p.smax, p.smax, fin, (int)N,
-                       (int)width, (int)n_frames, y, y_lens, nb, b);
-  else
-    hipLaunchKernelGGL(lm_search_gather_kernel<int64_t>, dim3((unsigned)N), dim3(256), 0, hs,
-                       reinterpret_cast<const int64_t *>(w + p.hist), 2 * width * p.smax, p.smax, fin, (int)N,
-                       (int)width, (int)n_frames, y, y_lens, nb, b);
+  hipLaunchKernelGGL(lm_search_gather_kernel<int16_t>, dim3((unsigned)N), dim3(256), 0, hs,
+                     reinterpret_cast<const int16_t *>(w + p.hist), 2 * width * p.smax, p.smax, fin, (int)N,
+                     (int)width, (int)n_frames, y, y_lens, nb, b);
   return (int)hipGetLastError();
 }

@@ -94,7 +94,10 @@ __host__ __device__ inline LmTabLayout lmtab_layout(int V, int W, int contexts) 
   LmTabLayout l;
   l.fmax_floats = 0;  // (the rows' largest factors are fetched with the pairs, after every frame: no staging)
   l.row_floats = (V + 1 + 3) & ~3;
-  l.rows_bytes = l.row_floats * 4 * kLmTabRows;
+  // (the ring, and room for one W-entry row of the output walk's checkpoint table, which overlays it
+  // once the workers have left: narrower than the ring unless the vocabulary is a handful of tokens)
+  const int walk_row = (W * 8 + 15) & ~15;
+  l.rows_bytes = l.row_floats * 4 * kLmTabRows > walk_row ? l.row_floats * 4 * kLmTabRows : walk_row;
   const int lists = W * PDT_WAVE * 8, small = lmtab_small_ints(W) * 4;
   const int consumer = consumer_scratch_bytes(W);
   l.utt_bytes = (l.rows_bytes + lists + small + consumer + kLmTabWaves * PDT_SURV_CAP * 8 + 128 + l.fmax_floats * 4 + 15) & ~15;  // (128: flags, row statistics)
@@ -611,8 +614,47 @@ static int64_t lm_table_trie_bytes(int64_t T, int64_t N, int64_t width) {
   return ((T + T / 32 + 1) * N * width * (int64_t)sizeof(int2) + 255) & ~(int64_t)255;
 }
 
+// Everything the launch decides from the sizes alone (host arithmetic, no device work): the LDS layout,
+// the checkpoint spacing and count, the kernel instance.  The (C + 1) x W table of the output walk
+// overlays the row ring, so the spacing doubles until that table fits: the ring holds at least one
+// W-entry row (lmtab_layout) and T < 2^24 leaves a single row at shift 24 -- the loop ends there at the
+// latest, whatever the sizes.  PDT_OK, or the code pdt_ctc_lm_table_search returns for these sizes.
+struct LmTabPlan {
+  pdt::LmTabLayout ly;
+  int ckpt_shift, ckpt_count;
+  int nr;       // the instance's 64-token chunks per row: 8, 16, 32, 48 or 80
+  int fixed_w;  // 16: the instance with the width as a constant, 0: the generic one
+};
+static int lm_table_plan(int64_t T, int64_t V, int64_t width, LmTabPlan &p) {
+  using namespace pdt;
+  if (T < 0 || V < 1 || width < 1) return PDT_E_ARG;
+  if (width > kMaxWidth || V + 1 > 80 * PDT_WAVE) return PDT_E_TOO_LONG;
+  if (T * width >= (1ll << 31) || T >= (1 << 24)) return PDT_E_TOO_LONG;
+  p.ly = lmtab_layout((int)V, (int)width, 0);
+  if ((size_t)p.ly.utt_bytes > 160 * 1024) return PDT_E_TOO_LONG;
+  int sh = 5;
+  while (sh < 24 && ((size_t)(T >> sh) + 1) * (size_t)width * sizeof(int2) > (size_t)p.ly.rows_bytes) ++sh;
+  if (((size_t)(T >> sh) + 1) * (size_t)width * sizeof(int2) > (size_t)p.ly.rows_bytes) return PDT_E_TOO_LONG;
+  p.ckpt_shift = sh;
+  p.ckpt_count = (int)(T >> sh) + 1;
+  const int chunks = (int)((V + 1 + PDT_WAVE - 1) / PDT_WAVE);
+  p.nr = chunks <= 8 ? 8 : chunks <= 16 ? 16 : chunks <= 32 ? 32 : chunks <= 48 ? 48 : 80;
+  p.fixed_w = width == 16 ? 16 : 0;
+  return PDT_OK;
+}
+
+int pdt_ctc_lm_table_search_plan(int64_t T, int64_t V, int64_t width, int32_t *plan6) {
+  LmTabPlan p{};
+  if (!plan6) return PDT_E_ARG;
+  if (const int rc = lm_table_plan(T, V, width, p)) return rc;
+  plan6[0] = p.ckpt_shift; plan6[1] = p.ckpt_count; plan6[2] = p.nr; plan6[3] = p.fixed_w;
+  plan6[4] = p.ly.rows_bytes; plan6[5] = p.ly.utt_bytes;
+  return PDT_OK;
+}
+
 int64_t pdt_ctc_lm_table_search_workspace_bytes(int64_t T, int64_t N, int64_t V, int64_t width) {
-  if (T < 0 || N < 0 || V < 1 || width < 1) return 0;
+  LmTabPlan p{};
+  if (N < 0 || lm_table_plan(T, V, width, p) != PDT_OK) return 0;
   return lm_table_trie_bytes(T, N, width) + 16;
 }
 
@@ -628,8 +670,9 @@ int pdt_ctc_lm_table_search(const float *logits, int64_t T, int64_t N, int64_t V
   if (contexts >= (1 << 30)) return PDT_E_TOO_LONG;  // (a context word keeps the row in 30 bits)
   if (N == 0) return PDT_OK;
   if (!y_lens || !y_probs || !factors || !factor_max || (T > 0 && (!logits || !workspace)) || (S > 0 && !y)) return PDT_E_ARG;
-  if (width > kMaxWidth || V + 1 > 80 * PDT_WAVE) return PDT_E_TOO_LONG;
-  if (T * width >= (1ll << 31) || N >= (1ll << 31) || T >= (1 << 24)) return PDT_E_TOO_LONG;
+  LmTabPlan plan{};
+  if (const int rc = lm_table_plan(T, V, width, plan)) return rc;
+  if (N >= (1ll << 31)) return PDT_E_TOO_LONG;
   LmTabArgs A{};
   CtcArgs &a = A.c;
   a.logits = logits; a.lg_st = lg_st; a.lg_sn = lg_sn; a.lg_sv = lg_sv;
@@ -642,25 +685,26 @@ int pdt_ctc_lm_table_search(const float *logits, int64_t T, int64_t N, int64_t V
   a.no_lean_extra = switches().ctc_lean_extra == 0 ? 1 : 0;
   A.ctx_base = (int)ctx_base; A.ctx_mod = (int)ctx_mod;
   A.factors = factors; A.fmax = factor_max; A.f_stride = f_stride; A.contexts = (int)contexts; A.sos_row = (int)sos_row; A.beta = beta; A.valid_mixture = valid_mixture;
-  const LmTabLayout ly = lmtab_layout((int)V, (int)width, (int)contexts);
-  if ((size_t)ly.utt_bytes > 160 * 1024) return PDT_E_TOO_LONG;
-  int sh = 5;  // checkpoint spacing: the (C + 1) x W table of the output walk overlays the row ring
-  while (((size_t)(T >> sh) + 1) * width * sizeof(int2) > (size_t)ly.rows_bytes) ++sh;
-  a.ckpt_shift = sh;
-  a.ckpt_count = (int)(T >> sh) + 1;
-  const int chunks = (int)((V + 1 + PDT_WAVE - 1) / PDT_WAVE);
-  if (a.W == 16) {
-    if (chunks <= 8) return launch_lm_table<8, 16>(A, ly, (hipStream_t)stream);
-    if (chunks <= 16) return launch_lm_table<16, 16>(A, ly, (hipStream_t)stream);
-    if (chunks <= 32) return launch_lm_table<32, 16>(A, ly, (hipStream_t)stream);
-    if (chunks <= 48) return launch_lm_table<48, 16>(A, ly, (hipStream_t)stream);
-    return launch_lm_table<80, 16>(A, ly, (hipStream_t)stream);
+  const LmTabLayout &ly = plan.ly;
+  a.ckpt_shift = plan.ckpt_shift;
+  a.ckpt_count = plan.ckpt_count;
+  hipStream_t hs = (hipStream_t)stream;
+  if (plan.fixed_w == 16) {
+    switch (plan.nr) {
+      case 8: return launch_lm_table<8, 16>(A, ly, hs);
+      case 16: return launch_lm_table<16, 16>(A, ly, hs);
+      case 32: return launch_lm_table<32, 16>(A, ly, hs);
+      case 48: return launch_lm_table<48, 16>(A, ly, hs);
+      default: return launch_lm_table<80, 16>(A, ly, hs);
+    }
   }
-  if (chunks <= 8) return launch_lm_table<8>(A, ly, (hipStream_t)stream);
-  if (chunks <= 16) return launch_lm_table<16>(A, ly, (hipStream_t)stream);
-  if (chunks <= 32) return launch_lm_table<32>(A, ly, (hipStream_t)stream);
-  if (chunks <= 48) return launch_lm_table<48>(A, ly, (hipStream_t)stream);
-  return launch_lm_table<80>(A, ly, (hipStream_t)stream);
+  switch (plan.nr) {
+    case 8: return launch_lm_table<8>(A, ly, hs);
+    case 16: return launch_lm_table<16>(A, ly, hs);
+    case 32: return launch_lm_table<32>(A, ly, hs);
+    case 48: return launch_lm_table<48>(A, ly, hs);
+    default: return launch_lm_table<80>(A, ly, hs);
+  }
 }
 
 }  // extern "C"

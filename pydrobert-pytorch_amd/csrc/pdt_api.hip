@@ -138,6 +138,8 @@ extern "C" {
 //     callers keeps its results (the version stays 12)
 // 14, then additively: pdt_ctc_prefix_search_wide, pdt_ctc_prefix_search_wide_workspace_bytes (the
 //     one-launch CTC search for beams of up to 128 prefixes, csrc/ctc_search_wide.hip)
+//     then: pdt_ctc_lm_table_search_plan, pdt_ctc_lookup_lm_search_lds_bytes (host arithmetic only);
+//     pdt_ctc_lm_table_search_workspace_bytes returns 0 for sizes the search does not take
 int pdt_amd_abi_version(void) { return 14; }
 
 int pdt_amd_set_switch(const char *name, int value) {

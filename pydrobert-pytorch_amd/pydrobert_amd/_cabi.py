@@ -22,7 +22,9 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # the gradient's dtype (a library of version 12 would read the arguments one place off).  14: the attention
 # entry points' lse holds two numbers per row, (2, R) (a library of version 13 wrote and read R).  The relaxed-
 # sampling entry points were added at 14 in the way of the first exception (the same test file pins 14 now; no
-# existing declaration changed), and so were those of the estimators (pdt_mc_reduce*, pdt_imh_chain).
+# existing declaration changed), and so were those of the estimators (pdt_mc_reduce*, pdt_imh_chain) and the
+# host-only plans of the searches with an n-gram model (pdt_ctc_lm_table_search_plan,
+# pdt_ctc_lookup_lm_search_lds_bytes).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -97,6 +99,7 @@ SIGNATURES = {
         [_P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _I64, _I64, _I64, _I64]
         + [_P, _I64, _I64, _I64, _P, _P, _P, _P, _P],
     ),
+    "pdt_ctc_lookup_lm_search_lds_bytes": (_I64, [_I64, _I64]),
     "pdt_ctc_lookup_lm_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64, _I64, _I64]),
     "pdt_ctc_lookup_lm_search": (
         _INT,
@@ -105,6 +108,7 @@ SIGNATURES = {
     ),
     "pdt_lm_factor_table": (_INT, [_P, _I64, _I64, _F, _INT, _P, _I64, _P]),
     "pdt_ctc_lm_table_search_workspace_bytes": (_I64, [_I64, _I64, _I64, _I64]),
+    "pdt_ctc_lm_table_search_plan": (_INT, [_I64, _I64, _I64, _P]),
     "pdt_ctc_lm_table_search": (
         _INT,
         [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _I64, _I64, _I64, _I64, _I64, _F, _INT, _P, _P, _P, _P, _P],

@@ -8,6 +8,7 @@ iterations in ``csrc/beam_step.hip`` and ``csrc/beam_search_table.hip``, through
 language model.  The step functions are in ``_step.py``, greedy search and sequence
 log-probabilities in ``_seqops.py``, the random walks in ``_walk.py``.
 """
+import ctypes
 import math
 import weakref
 from typing import Dict, Optional, Tuple
@@ -221,10 +222,10 @@ class CTCPrefixSearch(torch.nn.Module):
         return y, y_lens, nb + b
 
     @torch.jit.unused
-    def _searches_through_a_factor_table(self) -> bool:
+    def _searches_through_a_factor_table(self, n_frames: int) -> bool:
         """Of the searches :meth:`_fuses_lookup_lm` admits, those whose (contexts, V) factor table is
-        small enough: the search of csrc/ctc_lm_table.hip (PDT_CTC_LM_TABLE=0: the one of
-        csrc/ctc_lm_step.hip, for comparisons)."""
+        small enough and whose sizes the kernel's host plan takes: the search of csrc/ctc_lm_table.hip
+        (PDT_CTC_LM_TABLE=0: the one of csrc/ctc_lm_step.hip, for comparisons)."""
         lm = self.lm
         if not switches.get("PDT_CTC_LM_TABLE"):
             return False
@@ -232,7 +233,16 @@ class CTCPrefixSearch(torch.nn.Module):
         # (a row per context: U^(order - 1) of them -- 4 MB for a bigram model over 1000 tokens, 4 GB for a
         # trigram model: the card has 288)
         rows = (V + 1) ** (lm.max_ngram - 1)
-        return V + 1 <= 80 * 64 and rows < (1 << 30) and rows * V * 4 <= _FACTOR_TABLE_MAX_BYTES
+        if not (V + 1 <= 80 * 64 and rows < (1 << 30) and rows * V * 4 <= _FACTOR_TABLE_MAX_BYTES):
+            return False
+        return _lm_table_plan(n_frames, V, self.width) is not None
+
+    @torch.jit.unused
+    def _searches_from_one_call(self) -> bool:
+        """Of the searches :meth:`_fuses_lookup_lm` admits, those whose rows fit a workgroup's LDS in
+        csrc/ctc_lm_step.hip (two rows of V floats and the beam's tables in 160 KB: about twenty thousand
+        tokens); larger vocabularies go frame by frame, which takes any."""
+        return int(_cabi.lib().pdt_ctc_lookup_lm_search_lds_bytes(self.lm.vocab_size, self.width)) > 0
 
     @torch.jit.unused
     def _lm_table_search(
@@ -283,9 +293,10 @@ class CTCPrefixSearch(torch.nn.Module):
         if not torch.jit.is_scripting():
             # this package's n-gram model in the loop: the whole search from one call of the library
             if self.lm is not None and self.beta != 0.0 and n_frames > 0 and self._fuses_lookup_lm(logits):
-                if self._searches_through_a_factor_table():
+                if self._searches_through_a_factor_table(n_frames):
                     return self._lm_table_search(logits, lens, n_frames)
-                return self._lookup_lm_search(logits.softmax(2), lens, n_frames)
+                if self._searches_from_one_call():
+                    return self._lookup_lm_search(logits.softmax(2), lens, n_frames)
         probs = logits.softmax(2)
         # beam state: one empty prefix per utterance, all of its mass on "ends in blank"
         nb = torch.zeros((N, 1), device=device, dtype=dtype)
@@ -450,6 +461,16 @@ def _dense_table(lm: "LookupLanguageModel", device: torch.device):
         return table, stats, sos_row, U
 
     return _cached_table(_BIGRAM_TABLES if n1 == 1 else _CONTEXT_TABLES, lm, device, build)
+
+
+def _lm_table_plan(n_frames: int, V: int, width: int):
+    """``(checkpoint shift, checkpoints, chunks of the kernel instance, its constant width or 0, ring bytes,
+    LDS bytes)`` of the factor-table search for these sizes (include/pdt_amd.h: pdt_ctc_lm_table_search_plan;
+    host arithmetic only), ``None`` for sizes it does not take."""
+    plan = (ctypes.c_int32 * 6)()
+    if _cabi.lib().pdt_ctc_lm_table_search_plan(n_frames, V, width, plan) != _cabi.PDT_OK:
+        return None
+    return tuple(plan)
 
 
 def _factor_table(lm: "LookupLanguageModel", beta: float, valid_mixture: bool, device: torch.device):

@@ -23,7 +23,7 @@ __device__ unsigned long long *g_stamp_lds_dummy;
 #endif
 
 // Diagnostic build only (-DPDT_STATS): event counters (lane 0 of every wave; [16]: frames the steady
-// tier of ctc_frame decided)
+// tier of ctc_frame decided, [17]: frames in which its test held the bound of a short list's hidden second entry)
 #ifdef PDT_STATS
 __device__ unsigned long long g_stats[24];
 #define PDT_STAT(i) do { if (lane_id() == 0) atomicAdd(&g_stats[i], 1ull); } while (0)
@@ -369,14 +369,82 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
   // the steady tier decided the frame: new entry i is old entry i extended (the state update below
   // then needs none of its fetches by source lane)
   bool steady_f = false;
-  {  // scope of the lean tier's per-lane layout values
+  {  // scope of the steady tier's keys and the lean tier's per-lane layout values
+  const int G = Kp <= 16 ? 16 : 32;
+  // Steady tier: the beam is kept in rank order, so every prefix's best available extension (tot,
+  // non-increasing in k, times ONE list probability unless merges took entries away) is usually sorted
+  // already, and in most frames of a full beam it beats everything else -- a challenger gets in only by
+  // beating the K-th mass.  Then the result of the lean tier's sort is known without sorting: rank i is
+  // lane i.  Decided in the beam's OWN lanes, in front of the lean tier's 64-lane layout: lane k < 16
+  // forms the four candidates the layout would spread over lanes k, 16 + k, 32 + k, 48 + k from its own
+  // registers and three list reads -- key0 / key1 its first two available list entries (the same single
+  // products tot * tl_p[j], so the same bits; where a short list ends before the second one, the UPPER
+  // BOUND of the hidden entry: the mass with the list's last probability, key + 1 so it wins ties),
+  // key2 the last-token stream, key3 the non-extension; lanes that hold no valid beam entry contribute
+  // 0.  A steady frame reads nothing of the layout, and its seven crossbar fetches by source lane, the
+  // row selects and the sort key are built only for the frames that go on to the sort.
+  // The rule, on the EXACT keys: lanes 0 .. K-1 hold real key0 candidates (no upper bound of a hidden
+  // entry), their keys do not increase in lane order, and the key of lane K-1 is STRICTLY above every
+  // key1 / key2 / key3 (bounds take part with their + 1: stricter only).  Equal or nearly equal keys
+  // among lanes 0 .. K-1 are in place all the same: where the rounded sort ties, the lean tier ranks by
+  // exact key and then by the full tiers' tie order, the lowest flat candidate index (trank below) --
+  // for a row-0 candidate kb * 128 + 2 j + 1, which grows with the lane whatever j is, so lane order is
+  // the order it would produce (a pair of prefixes that came by equal masses once ties in every later
+  // frame, and on the sort's buckets each of those frames paid the sort, the pair fix-up and the
+  // fetches to get back what was there).  An equal key among the others may have the lower index (a
+  // second entry of a lower prefix has): equality there must not pass.  Masses that have underflowed
+  // into the lowest bucket stay with the sort and the full tiers (the K-th key must lie above it; the
+  // lean tier asks the same of its ties).
+  // No second entry wins, no bound wins, no tie is out of place: the lean tier would select exactly these.
+  // (wave-uniform: ballots, readlanes and scalar compares; one branch with all that depends on it inside)
+  // Shared-list forms only (ctc_search.hip, ctc_rowreg.hip): the conditions hold for per-prefix lists
+  // just as well, but the step functions and the bigram-table search carry no switch to compare with.
+  bool steady = false;
+  unsigned key0 = 0u;
+  int tok0 = 0;
+  // (the switch in the outer condition: as the last term of `steady` it cost twenty more scalar spills)
+  if (!DENSE && G == 16 && M <= 32 && K <= 16 && !a.no_steady) {
+    const unsigned av0 = (unsigned)avail, av1 = av0 & (av0 - 1u);
+    const bool bound1 = !full_list && av1 == 0u;
+    const int j0 = av0 ? __builtin_ctz(av0) : 0;
+    const int j1 = av1 ? __builtin_ctz(av1) : (bound1 ? c_list - 1 : 0);
+    tok0 = L.tl_tok[j0];
+    const float p0 = L.tl_p[j0], p1 = L.tl_p[j1];
+    // (a hidden first entry -- a short list with nothing left for this prefix -- is not real: the test fails)
+    const bool real0 = valid_beam && av0 != 0u;
+    key0 = real0 ? fkey_nonneg(tot * p0) : 0u;
+    const unsigned key1 = (valid_beam && (av1 != 0u || bound1)) ? fkey_nonneg(tot * p1) + (bound1 ? 1u : 0u) : 0u;
+#ifdef PDT_STATS
+    if (__ballot(valid_beam && bound1) != 0ull) PDT_STAT(17);
+#endif
+    // (an open stream belongs to a valid beam entry: s1_open / s2_open start as valid_beam)
+    const unsigned key2 = s1_open ? fkey_nonneg(m1) : 0u, key3 = s2_open ? fkey_nonneg(m2) : 0u;
+    const unsigned key_next = (unsigned)__builtin_amdgcn_mov_dpp((int)key0, 0x101, 0xf, 0xf, true);  // row_shl:1
+    const unsigned first_k = (1u << K) - 1u;
+    const unsigned real_m = (unsigned)__ballot(real0) & 0xFFFFu;
+    const unsigned desc = (unsigned)__ballot(key0 >= key_next) & (first_k >> 1);
+    const unsigned rest = row0_max_u32(max(max(key1, key2), key3));
+    const unsigned kth = (unsigned)__builtin_amdgcn_readlane((int)key0, K - 1);
+    // (64: the largest key of the lowest bucket)
+    steady = real_m == first_k && desc == (first_k >> 1) && kth > max(rest, 64u);
+  }
+  if (steady) {
+    PDT_STAT(16);
+    steady_f = true;
+    if (lane < K) {
+      new_src = lane;
+      new_tok = tok0;
+      new_kind = 0;
+      new_mass = fkey_nonneg_inv(key0);
+    }
+    selected = true;
+  } else {  // the lean tier's layout and sort (not indented: the lean tier as it was)
   // All 64 lanes hold candidates: lane = G * r + k carries, for prefix k, three of its
   // candidates (slots s = 0..2, "entry" e = r + R * s): entries 0 .. 3R-3 are the first
   // available list entries of stream 0 in order, entry 3R-2 is stream 1, entry 3R-1 stream 2.
   // A prefix's resident entries are consumed in order (they are sorted), so a round is just
   // a wave max + clearing the winning slot; only when a prefix uses up ALL its resident
   // stream-0 entries are its slots refilled with the next 3R-2.
-  const int G = Kp <= 16 ? 16 : 32;
   const int kb = lane & (G - 1), rr = lane >> (G == 16 ? 4 : 5);  // (a shift, not a division by a runtime G)
   const int ksrc = kb < Kp ? kb : 0;
   const bool kvalid = kb < Kp && (shfl_i((int)valid_beam, ksrc) != 0);
@@ -416,55 +484,6 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
     // their rounded keys are >= 64).
     PDT_STAMP(7);
     const unsigned kt = has ? (((keyL + 63u) & ~63u) | (63u - (unsigned)lane)) : (63u - (unsigned)lane);
-    // Steady tier: the beam is kept in rank order, so row 0 (every prefix's best available extension:
-    // tot_k, non-increasing in k, times ONE list probability unless merges took entries away) is usually
-    // sorted already, and in most frames of a full beam it beats everything else -- a challenger gets in
-    // only by beating the K-th mass.  Then the sort's result is known without sorting: rank i is lane i.
-    // Decided on the EXACT keys keyL: lanes 0 .. K-1 hold real row-0 candidates (no upper bound of a
-    // hidden entry), their keys do not increase in lane order, and the key of lane K-1 is STRICTLY above
-    // every key of rows 1-3 (bounds take part with their + 1: stricter only).  Equal or nearly equal
-    // keys among lanes 0 .. K-1 are in place all the same: where the rounded sort ties, the lean tier
-    // ranks by exact key and then by the full tiers' tie order, the lowest flat candidate index
-    // (trank below) -- for a row-0 candidate kb * 128 + 2 j + 1, which grows with the lane whatever j
-    // is, so lane order is the order it would produce (a pair of prefixes that came by equal masses
-    // once ties in every later frame, and on the sort's buckets each of those frames paid the sort,
-    // the pair fix-up and the fetches to get back what was there).  An equal key in rows 1-3 may have
-    // the lower index (a row-1 entry of a lower prefix has): equality there must not pass.  Masses that
-    // have underflowed into the lowest bucket stay with the sort and the full tiers (the K-th key must
-    // lie above it; the lean tier asks the same of its ties).
-    // No row-1 entry wins, no bound wins, no tie is out of place: the lean tier would select exactly these.
-    // (wave-uniform: ballots, readlanes and scalar compares; one branch with all that depends on it inside)
-    // Shared-list forms only (ctc_search.hip, ctc_rowreg.hip): the conditions hold for per-prefix lists
-    // just as well, but the step functions and the bigram-table search carry no switch to compare with.
-    bool steady = false;
-    // (the switch in the outer condition: as the last term of `steady` it cost twenty more scalar spills)
-    if (!DENSE && K <= 16 && !a.no_steady) {
-      const unsigned key_next = (unsigned)__builtin_amdgcn_mov_dpp((int)keyL, 0x101, 0xf, 0xf, true);  // row_shl:1
-      const unsigned first_k = (1u << K) - 1u;
-      const unsigned row0_has = (unsigned)__ballot(has) & 0xFFFFu, row0_hid = (unsigned)__ballot(hidden) & first_k;
-      const unsigned desc = (unsigned)__ballot(keyL >= key_next) & (first_k >> 1);
-      unsigned rmax = keyL;  // row maxima in lanes 15, 31, 47, 63
-      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(1)>((int)rmax, 0));
-      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(2)>((int)rmax, 0));
-      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(4), 0xf, 0xe>((int)rmax, 0));
-      rmax = max(rmax, (unsigned)dpp_or<PDT_DPP_ROW_SHR(8), 0xf, 0xc>((int)rmax, 0));
-      const unsigned rest = max(max((unsigned)__builtin_amdgcn_readlane((int)rmax, 31), (unsigned)__builtin_amdgcn_readlane((int)rmax, 47)),
-                                (unsigned)__builtin_amdgcn_readlane((int)rmax, 63));
-      const unsigned kth = (unsigned)__builtin_amdgcn_readlane((int)keyL, K - 1);
-      // (64: the largest key of the lowest bucket)
-      steady = row0_has == first_k && row0_hid == 0u && desc == (first_k >> 1) && kth > max(rest, 64u);
-    }
-    if (steady) {
-      PDT_STAT(16);
-      steady_f = true;
-      if (lane < K) {
-        new_src = lane;
-        new_tok = tokL;
-        new_kind = 0;
-        new_mass = fkey_nonneg_inv(keyL);
-      }
-      selected = true;
-    } else {  // the sort decides (not indented: the lean tier as it was)
     const unsigned st = wave_sort_desc<unsigned>(kt);
     PDT_STAMP(8);
     int wl = 63 - (int)(st & 63u);
@@ -614,8 +633,8 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
       }
       selected = true;
     }
-    }  // !steady
   }
+  }  // !steady
 
   }
   bool list_sufficed = true;

@@ -1,6 +1,7 @@
 """Fuzz of the lean tier's side paths (mid tier, exact re-ranking, all-pairs prefix update) against the full
 tiers / per-descendant loops: the same search with PDT_CTC_LEAN_EXTRA = 1 and 0, torch.equal on all outputs --
-and of the steady tier in front of the lean sort against the sort: PDT_CTC_STEADY = 1 and 0, likewise.
+and of the steady tier in front of the lean sort against the sort: PDT_CTC_STEADY = 1 and 0, likewise -- and of the
+two steady frames decided at once against the frame-by-frame steady tier: PDT_CTC_TWOFRAME = 1 and 0, likewise.
 python profiles/tools/fuzz_tiers.py [seed] [cases]"""
 import sys, numpy as np, torch
 sys.path.insert(0, "."); sys.path.insert(0, "pydrobert-pytorch_amd")
@@ -9,7 +10,7 @@ dev = torch.device("cuda:0")
 seed = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 cases = int(sys.argv[2]) if len(sys.argv) > 2 else 300
 rng = np.random.default_rng(seed)
-bad = bad_steady = 0
+bad = bad_steady = bad_two = 0
 for it in range(cases):
     V = int(rng.choice([256, 256, 257, 300, 128, 64, 1000, 5000, 40])); W = int(rng.choice([16, 16, 16, 8, 12, 5, 2, 32]))
     T = int(rng.choice([20, 64, 130, 300, 600])); N = int(rng.integers(1, 40))
@@ -40,6 +41,12 @@ for it in range(cases):
     switches.set("PDT_CTC_STEADY", 0)
     outs.append(F.ctc_prefix_search(x, W, lens))
     switches.set("PDT_CTC_STEADY", 1)
+    switches.set("PDT_CTC_TWOFRAME", 0)
+    two_off = F.ctc_prefix_search(x, W, lens)
+    switches.set("PDT_CTC_TWOFRAME", 1)
+    if not all(torch.equal(p, q) for p, q in zip(outs[0], two_off)):
+        bad_two += 1
+        print("TWOFRAME MISMATCH case", it, "V", V, "W", W, "T", T, "N", N, "kind", kind, flush=True)
     if not all(torch.equal(p, q) for p, q in zip(outs[0], outs[2])):
         bad_steady += 1
         print("STEADY MISMATCH case", it, "V", V, "W", W, "T", T, "N", N, "kind", kind, flush=True)
@@ -53,7 +60,8 @@ for it in range(cases):
         print("MISMATCH case", it, "V", V, "W", W, "T", T, "N", N, "kind", kind, "utterances", sorted(set(dn + dy))[:6],
               "probs", p1[n].tolist(), p0[n].tolist(), "lens", l1[n].tolist(), l0[n].tolist(), flush=True)
 switches.set("PDT_CTC_LEAN_EXTRA", 1)
-print("tier fuzz: %d cases, %d mismatches; steady tier on / off: %d mismatches" % (cases, bad, bad_steady), flush=True)
+print("tier fuzz: %d cases, %d mismatches; steady tier on / off: %d mismatches; two frames at once on / off: %d mismatches"
+      % (cases, bad, bad_steady, bad_two), flush=True)
 
 # ---- the same two settings through the searches with a bigram model (per-prefix lists: DENSE ctc_frame) ----
 sys.path.insert(0, "tests")

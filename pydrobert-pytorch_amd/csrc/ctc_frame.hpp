@@ -23,7 +23,8 @@ __device__ unsigned long long *g_stamp_lds_dummy;
 #endif
 
 // Diagnostic build only (-DPDT_STATS): event counters (lane 0 of every wave; [16]: frames the steady
-// tier of ctc_frame decided, [17]: frames in which its test held the bound of a short list's hidden second entry)
+// tier of ctc_frame decided, [17]: frames in which its test held the bound of a short list's hidden second entry,
+// [18]: PAIRS of frames ctc_two_steady_frames committed -- steady frames are [16] + 2 * [18] --, [19]: pairs it rejected)
 #ifdef PDT_STATS
 __device__ unsigned long long g_stats[24];
 #define PDT_STAT(i) do { if (lane_id() == 0) atomicAdd(&g_stats[i], 1ull); } while (0)
@@ -71,6 +72,9 @@ struct CtcArgs {
   // PDT_CTC_STEADY=0: no frame is decided by the steady tier in front of the lean tier's sort (same
   // results, same kernel instance; the tests compare the two).  Shared-list searches only.
   int no_steady;
+  // PDT_CTC_TWOFRAME=0: the two-frames-per-pass instance decides every frame by itself, none in pairs by
+  // ctc_two_steady_frames (same results, same kernel instance; the tests compare the two)
+  int no_twoframe;
 };
 
 struct Beam {
@@ -1081,6 +1085,130 @@ __device__ __forceinline__ bool ctc_frame(Beam &bm, const float *p, const float 
   wave_sync();
   PDT_STAMP(5);
   return list_sufficed;
+}
+
+// TWO steady frames of the trie form at once (the two-frames-per-pass instance of ctc_search.hip: shared
+// lists, W = K = 16, M = 32, frames t and t + 1 in the neighbouring ring slots `slot_t` and `slot_t +
+// slot_bytes`, both handed over by one producer pass).  A steady frame is straight-line code in 16 of the
+// wave's 64 lanes, and its result is known in closed form -- new entry k is old entry k extended by its
+// best available token tok0, mass tot * tl_p[j0], nothing ending in blank -- so frame t + 1 can be set up
+// before frame t is committed: row 0 (lanes 0-15) holds frame t, row 1 (lanes 16-31) frame t + 1 on the
+// beam frame t WOULD leave, and the masses, the four keys, the steady tier's test and the trie store run
+// once for both.  Taken only when the beam is full and holds no strict-prefix relation (then ctc_frame's
+// merge loop is empty, `add` is 0, every stream is open, and a steady frame leaves no relation behind
+// either: a + x is a prefix of b + y only if a is one of b) and BOTH frames pass the steady tier's test
+// term for term (ctc_frame above has the rule).  Every mass is the same single product of the same
+// operands as there, in another lane; the list, the bounds and the normaliser of frame t + 1 are read
+// from its own slot.
+// Returns whether it committed both frames.  False: nothing has changed -- the beam, the trie, `info`, the
+// next-token tables -- and the caller runs ctc_frame on t and on t + 1 as if this had not been called.
+// True: the beam is the one after frame t + 1, the 32 trie records of both frames are stored; `info` and
+// the next-token tables are not written (a beam without relations reads neither, and two of the caller's
+// table swaps are none).  Lanes 16 and up of the beam are left with values no frame reads.
+template <int V, int W>
+__device__ __forceinline__ bool ctc_two_steady_frames(Beam &bm, unsigned char *slot_t, const int slot_bytes,
+                                                      const int row_floats, const int pos_bytes, const int t,
+                                                      int2 *trie_u) {
+  static_assert(W == 16 && V >= 2 * W && V + 1 >= W, "two rows of 16 beam entries, lists of K + K' = 32 entries");
+  constexpr int K = W, M = 2 * W;
+  int lane = lane_id();
+  asm volatile("" : "+v"(lane));
+  // ---- entry: 16 valid entries, none a strict prefix of another -------------------------------------
+  // (bitwise: no short-circuit branches for two compares)
+  if (__ballot((lane < W) & (!(bm.nb + bm.b > -PDT_INF) | ((bm.isp & ~(1u << lane)) != 0u))) != 0ull) {
+    PDT_STAT(19);
+    return false;
+  }
+  // this lane's slot: frame t in rows 0 (and 2, 3: never looked at), frame t + 1 in row 1
+  const bool row1 = lane >= W;
+  const unsigned char *sb = slot_t + (row1 ? slot_bytes : 0);
+  const float *p = reinterpret_cast<const float *>(sb);
+  const int *tl_tok = reinterpret_cast<const int *>(sb + row_floats * 4);
+  const float *tl_p = reinterpret_cast<const float *>(tl_tok + PDT_WAVE);
+  const unsigned char *pos = reinterpret_cast<const unsigned char *>(tl_p + PDT_WAVE);
+  const float *hdr = reinterpret_cast<const float *>(pos + pos_bytes);
+  const float inv = hdr[0];
+  const int c_list = min(__float_as_int(hdr[2]), M);
+  const bool full_list = c_list >= M;
+  const unsigned have = c_list >= 32 ? ~0u : ((1u << c_list) - 1u);
+  // ---- row 0, frame t: the token and the mass every entry would take -----------------------------------
+  float nb = bm.nb, b = bm.b;
+  int last = bm.last;
+  {
+    const int lastc = min(max(last, 0), V - 1);
+    const unsigned q = pos[lastc];
+    const unsigned av0 = have & ~(unsigned)(1ull << (q & 63u));
+    const int j0 = av0 ? __builtin_ctz(av0) : 0;
+    const int tok0 = tl_tok[j0];
+    const float x = (nb + b) * tl_p[j0];
+    // ---- cross-row move (v_permlane16_swap, both operands the same: the first result is rows 0, 0, 2, 2)
+    const auto rx = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    const auto rt = __builtin_amdgcn_permlane16_swap((unsigned)tok0, (unsigned)tok0, false, false);
+    // ---- row 1, frame t + 1: entry k is (nb, b, last) = (tot * p0, 0, tok0) of row 0's lane k ----------
+    nb = row1 ? __uint_as_float(rx[0]) : nb;
+    b = row1 ? 0.0f : b;
+    last = row1 ? (int)rt[0] : last;
+  }
+  // ---- both rows together: ctc_frame's masses and the steady tier's keys, each on its own slot ---------
+  const int lastc = min(max(last, 0), V - 1);
+  const float p_blank = p[V] * inv;
+  const float pl = p[lastc] * inv;
+  const unsigned q = pos[lastc];
+  const float tot = nb + b;
+  const float B = tot * p_blank;
+  const float NB = nb * pl;  // (+ add, which is 0 without relations: NB >= +0 is unchanged by it)
+  const float m1 = b * pl;
+  const float m2 = NB + B;
+  const unsigned av0 = have & ~(unsigned)(1ull << (q & 63u)), av1 = av0 & (av0 - 1u);
+  const bool bound1 = !full_list && av1 == 0u;
+  const int j0 = av0 ? __builtin_ctz(av0) : 0;
+  const int j1 = av1 ? __builtin_ctz(av1) : (bound1 ? c_list - 1 : 0);
+  const int tok0 = tl_tok[j0];
+  const float p0 = tl_p[j0], p1 = tl_p[j1];
+  const float x0 = tot * p0;
+  const bool real0 = av0 != 0u;
+  const unsigned key0 = real0 ? fkey_nonneg(x0) : 0u;
+  const unsigned key1 = (av1 != 0u || bound1) ? fkey_nonneg(tot * p1) + (bound1 ? 1u : 0u) : 0u;
+  const unsigned key2 = fkey_nonneg(m1), key3 = fkey_nonneg(m2);
+  const unsigned key_next = (unsigned)__builtin_amdgcn_mov_dpp((int)key0, 0x101, 0xf, 0xf, true);  // row_shl:1
+  const unsigned real_m = (unsigned)__ballot(real0);
+  const unsigned desc = (unsigned)__ballot(key0 >= key_next) | 0x80008000u;
+  // (the row maxima of all four rows by the steps of row0_max_u32: lanes 15 and 31 hold rows 0 and 1)
+  unsigned v = max(max(key1, key2), key3);
+  v = max(v, (unsigned)dpp_or<PDT_DPP_ROW_SHR(1)>((int)v, 0));
+  v = max(v, (unsigned)dpp_or<PDT_DPP_ROW_SHR(2)>((int)v, 0));
+  v = max(v, (unsigned)dpp_or<PDT_DPP_ROW_SHR(4), 0xf, 0xe>((int)v, 0));
+  v = max(v, (unsigned)dpp_or<PDT_DPP_ROW_SHR(8), 0xf, 0xc>((int)v, 0));
+  const unsigned rest_a = (unsigned)__builtin_amdgcn_readlane((int)v, K - 1);
+  const unsigned rest_b = (unsigned)__builtin_amdgcn_readlane((int)v, W + K - 1);
+  const unsigned kth_a = (unsigned)__builtin_amdgcn_readlane((int)key0, K - 1);
+  const unsigned kth_b = (unsigned)__builtin_amdgcn_readlane((int)key0, W + K - 1);
+  // (64: the largest key of the lowest bucket)
+  if (!((real_m & desc) == ~0u && kth_a > max(rest_a, 64u) && kth_b > max(rest_b, 64u))) {
+    PDT_STAT(19);
+    return false;
+  }
+  PDT_STAT(18);
+#ifdef PDT_STATS
+  {
+    const unsigned bm_ = (unsigned)__ballot(bound1);
+    if ((bm_ & 0xFFFFu) != 0u) PDT_STAT(17);
+    if ((bm_ >> 16) != 0u) PDT_STAT(17);
+  }
+#endif
+  // ---- commit: 32 trie records (row 1's parent is the node row 0 creates), then the beam after t + 1 ----
+  if (lane < 2 * W)
+    *reinterpret_cast<int2 *>(reinterpret_cast<char *>(trie_u) + (unsigned)(t * W + lane) * 8u) =
+        make_int2(row1 ? t * W + lane - W : bm.node, tok0);
+  // (the second result of the swap is rows 1, 1, 3, 3: row 1's mass and token in lanes 0-15)
+  const auto bx = __builtin_amdgcn_permlane16_swap(__float_as_uint(x0), __float_as_uint(x0), false, false);
+  const auto bt = __builtin_amdgcn_permlane16_swap((unsigned)tok0, (unsigned)tok0, false, false);
+  bm.nb = __uint_as_float(bx[1]);
+  bm.b = 0.0f;
+  bm.last = (int)bt[1];
+  bm.len += 2;
+  bm.node = (t + 1) * W + lane;
+  return true;
 }
 
 // Output walk of the one-kernel searches, second step: the (C + 1) x W segments between consecutive

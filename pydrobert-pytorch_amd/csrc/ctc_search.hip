@@ -615,6 +615,11 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
   constexpr bool kFullFromStart = WC > 0 && VC > 0 && VC + 1 >= WC;
   int Kp = kFullFromStart ? WC : 1;
   int fail_score = 0, full_mode = 0;
+  // Gate of the two-frames-at-once attempt (a scalar, like fail_score): bits 8 and up count the attempts
+  // rejected in a row (capped at 5), the low byte the pairs still to pass over without an attempt -- none
+  // after one or two rejections, then 4, 12 and 28: an input whose pairs never qualify (blank-dominated
+  // rows: relations everywhere) pays one attempt in 29 pairs; a committed pair clears it.
+  int two_gate = 0;
   // (32-frame checkpoints in the constant-shape instance: the launcher checks)
   const int ckpt_shift = (WC > 0 && VC > 0) ? 5 : a.ckpt_shift;
 #ifdef PDT_STAMPS
@@ -658,6 +663,43 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
     // are then a compare where used, not scalar pairs kept across the frame and spilled to lanes)
     int lane_t = lane;
 #ifndef PDT_SKIP_CONSUMER  // diagnostic build: producer-side cost alone
+    // feedback to the producers: a complete selection costs the producer about what two list
+    // completions cost this wave, so the balance is at one completed list in two frames: +1
+    // per frame this wave had to complete a short list, -1 per frame it did not (0 .. 32);
+    // complete lists above 16, short ones again below 4
+    auto list_feedback = [&](const int enough_s) {
+      fail_score = enough_s ? max(fail_score - 1, 0) : min(fail_score + 1, 32);
+      const int wf = fail_score > 16 ? 1 : (fail_score < 4 ? 0 : full_mode);
+      if (wf != full_mode) {
+        full_mode = wf;
+        asm volatile("" : "+v"(lane_t));
+        if (lane_t == 0) __hip_atomic_store(want_full, wf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    };
+    // Two steady frames at once (ctc_two_steady_frames): the producer of this instance hands frames over
+    // in even-aligned pairs, so the acquire above covers frame t + 1 as well.  Both frames or neither;
+    // then the frame counter, the ring slot and the feedback (two frames whose lists sufficed) move on by
+    // one here and by the loop's own step below -- an even-aligned pair ends on a checkpoint, never
+    // straddles one.  (The switches in the outer condition, as no_steady is in ctc_frame.)
+    bool single = true;
+    if constexpr (PAIR) {
+      if ((t & 1) == 0 && t + 1 < Tn && !a.no_steady && !a.no_twoframe && !(readlane_f(bm.nb + bm.b, 0) == 0.0f)) {
+        if ((two_gate & 0xFF) != 0) {
+          --two_gate;
+        } else if (ctc_two_steady_frames<VC, WC>(bm, ring + sl * rl.slot_bytes, rl.slot_bytes, rl.row_floats, rl.pos_bytes, t, L.trie_u)) {
+          list_feedback(1);
+          list_feedback(1);
+          ++t;
+          ++sl;
+          single = false;
+          two_gate = 0;
+        } else {
+          const int lvl = min((two_gate >> 8) + 1, 5);
+          two_gate = (lvl << 8) | (lvl < 3 ? 0 : (1 << lvl) - 4);
+        }
+      }
+    }
+    if (single) {
     // Every mass has underflowed to 0 (the beam is ordered, so entry 0 holds the largest): every
     // candidate of this and all later frames has mass 0 too, the reference's top-k over them is
     // a tie artefact, and nothing is left to decide -- the beam stays as it is.  (float32
@@ -673,19 +715,9 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
       L.nxt_new = tmp;
       if (!kFullFromStart) Kp = W;
     }
-    // feedback to the producers: a complete selection costs the producer about what two list
-    // completions cost this wave, so the balance is at one completed list in two frames: +1
-    // per frame this wave had to complete a short list, -1 per frame it did not (0 .. 32);
-    // complete lists above 16, short ones again below 4
     // (through a scalar: `enough` is wave-uniform but arrives as a lane mask, and the counter and
     // mode below would live in vector registers -- a dozen vector instructions per frame)
-    const int enough_s = __builtin_amdgcn_readfirstlane(enough ? 1 : 0);
-    fail_score = enough_s ? max(fail_score - 1, 0) : min(fail_score + 1, 32);
-    const int wf = fail_score > 16 ? 1 : (fail_score < 4 ? 0 : full_mode);
-    if (wf != full_mode) {
-      full_mode = wf;
-      asm volatile("" : "+v"(lane_t));
-      if (lane_t == 0) __hip_atomic_store(want_full, wf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    list_feedback(__builtin_amdgcn_readfirstlane(enough ? 1 : 0));
     }
 #else
     ns = nt = nk = 0; (void)s;
@@ -907,6 +939,7 @@ int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, 
   a.exact_div = switches().ctc_exact_div == 1 ? 1 : 0;
   a.no_lean_extra = switches().ctc_lean_extra == 0 ? 1 : 0;
   a.no_steady = switches().ctc_steady == 0 ? 1 : 0;  // (no part of the plan: both values take the same instance)
+  a.no_twoframe = (switches().ctc_twoframe == 0 || a.no_steady) ? 1 : 0;  // (likewise)
   // (contiguous rows: the register form addresses a row as base + immediates)
   if (ctc_rowreg_applies(a.V, a.W) && lg_sv == 1) return launch_ctc_rowreg(a, (hipStream_t)stream);
   CtcPlan plan;

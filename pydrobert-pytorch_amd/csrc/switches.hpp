@@ -18,6 +18,8 @@ struct Switches {
   int ctc_lean_extra;  // PDT_CTC_LEAN_EXTRA 1  CTC frame: one-prefix and tie frames decided beside the lean tier (0: by the full tiers, same results)
   int ctc_steady;      // PDT_CTC_STEADY     1  CTC search without a model: frames whose best extensions are in rank order and beat everything
                        //                       else skip the lean tier's sort (0: every lean frame sorts; same kernel instance, same bits)
+  int ctc_twoframe;    // PDT_CTC_TWOFRAME   1  ... at V = 256, W = 16: two steady frames of a producer pass decided at once, one per 16-lane row
+                       //                       (0: frame by frame; same kernel instance, same bits; PDT_CTC_STEADY=0 implies 0)
 };
 
 Switches &switches();

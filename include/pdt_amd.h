@@ -939,6 +939,35 @@ int pdt_relaxed_gumbel(int op, int dtype, const void *param, int64_t B, int64_t 
 int pdt_relaxed_bernoulli(int op, int dtype, const void *param, int64_t B, int64_t p_sr, int64_t p_sv,
                           const void *in1, const void *in2, int64_t R, int64_t V, void *out, void *stream);
 
+/* The backward of the methods above, one launch each (two in the parts form).  g is the gradient of the
+ * method's result, dense: (R,) for the Gumbel methods that reduce (ops 2, 4, 5), (R, V) otherwise; param,
+ * in1 and in2 are the forward's.  grad_param is (B, V) dense, summed over the S = R / B sample rows that
+ * read each parameter row (float64 sums in one fixed order: no atomics, the same bits on every call);
+ * grad_in1 is (R, V) dense, the gradient of z (op 4) or zcond (op 5).  Either may be null, not both.  The
+ * arithmetic is that of the host's torch bodies in the data's type: masks that they multiply by are
+ * products, masks that they select with are selects (csample: zero on the hot index, where the min guard
+ * holds and where p is clamped; clog_prob: zero for a row whose b is not the one-hot of zcond's arg-max).
+ * The sums over b of csample and clog_prob (log v_k, z_k) run over the nonzeros of b.
+ * pdt_relaxed_backward_parts(R, B, V): P, the parts the S sample rows are cut into so that few parameter
+ * rows with many samples still fill the device; P > 1 needs a workspace of
+ * pdt_relaxed_backward_workspace_bytes (P * B * V float64; 0 for P == 1; PDT_E_ARG for an unknown dtype)
+ * and a second launch that adds the parts in their order.  0 for an empty size or R % B != 0.
+ * PDT_E_ARG, before any launch: an unknown op or dtype, op 1 (threshold has no derivative), B < 1,
+ * R % B != 0, both gradients null, grad_in1 for an op other than 4 and 5, a missing g, param or in1, a
+ * missing in2 for ops 3 and 5, a missing ws when P > 1.  R == 0 or V == 0 is OK (nothing to do).
+ * PDT_E_TOO_LONG when V exceeds 2^31 - 513. */
+int pdt_relaxed_backward_parts(int64_t R, int64_t B, int64_t V);
+
+int64_t pdt_relaxed_backward_workspace_bytes(int dtype, int64_t R, int64_t B, int64_t V);
+
+int pdt_relaxed_gumbel_backward(int op, int dtype, const void *g, const void *param, int64_t B, int64_t p_sr,
+                                int64_t p_sv, const void *in1, const void *in2, int64_t R, int64_t V,
+                                void *grad_param, void *grad_in1, void *ws, void *stream);
+
+int pdt_relaxed_bernoulli_backward(int op, int dtype, const void *g, const void *param, int64_t B, int64_t p_sr,
+                                   int64_t p_sv, const void *in1, const void *in2, int64_t R, int64_t V,
+                                   void *grad_param, void *grad_in1, void *ws, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Sample-axis reductions of the Monte Carlo estimators (reference _mc.py:145-173, 230-233, 297-301,
  * 390-404, 530-564; _enumerate_estimator.py:68-77): the whole formula of a column in one launch, its

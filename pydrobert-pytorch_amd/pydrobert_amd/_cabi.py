@@ -24,7 +24,8 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # sampling entry points were added at 14 in the way of the first exception (the same test file pins 14 now; no
 # existing declaration changed), and so were those of the estimators (pdt_mc_reduce*, pdt_imh_chain) and the
 # host-only plans of the searches with an n-gram model (pdt_ctc_lm_table_search_plan,
-# pdt_ctc_lookup_lm_search_lds_bytes).
+# pdt_ctc_lookup_lm_search_lds_bytes) and the backward of relaxed sampling (pdt_relaxed_backward_parts,
+# pdt_relaxed_backward_workspace_bytes, pdt_relaxed_gumbel_backward, pdt_relaxed_bernoulli_backward).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -232,6 +233,14 @@ SIGNATURES = {
     "pdt_relaxed_rows_per_block": (_INT, [_I64]),
     "pdt_relaxed_gumbel": (_INT, [_INT, _INT, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
     "pdt_relaxed_bernoulli": (_INT, [_INT, _INT, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
+    "pdt_relaxed_backward_parts": (_INT, [_I64, _I64, _I64]),
+    "pdt_relaxed_backward_workspace_bytes": (_I64, [_INT, _I64, _I64, _I64]),
+    "pdt_relaxed_gumbel_backward": (
+        _INT, [_INT, _INT, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P, _P],
+    ),
+    "pdt_relaxed_bernoulli_backward": (
+        _INT, [_INT, _INT, _P, _P, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P, _P, _P],
+    ),
     "pdt_mc_reduce_plan": (_INT, [_I64, _I64, _I64, _I64]),
     "pdt_mc_reduce": (_INT, [_INT, _INT, _INT, _INT, _I64, _I64, _P, _P, _P, _P, _P]),
     "pdt_mc_reduce_backward": (_INT, [_INT, _INT, _INT, _INT, _I64, _I64, _P, _P, _P, _P, _P, _P]),

@@ -7,16 +7,24 @@ drawn here with ``torch.rand`` / ``torch.rand_like`` and handed to the kernels a
 governs every draw, and on the CPU a seed reproduces the reference's stream.  Other dtypes, CPU tensors, and a
 discrete sample ``b`` that itself wants a gradient take torch bodies that restate the reference's formulas.
 
-Gradients.  The backward of every method is composed of differentiable torch ops from the saved inputs (the
-Jacobians are diagonal: elementwise work and a ``sum_to_size`` onto the parameter), so it is differentiable
-again -- in the incoming gradient, which RELAX needs, and in the parameters and relaxed samples.  ``threshold``
-is computed without gradient, as in the reference.  An input with no derivative here (the noise) raises
-rather than receive a silent zero.
+Gradients.  The backward of every method is an operator of its own, ``pydrobert_amd::relaxed_backward``: one
+launch of the backward kernels of ``csrc/relaxed.hip`` (the Jacobians are diagonal) that writes the gradient of
+the relaxed sample, where the method has one, and the gradient of the parameter ALREADY summed over the sample
+rows, in float64 and in one fixed order; a second small launch adds partial sums where few parameter rows have
+many samples.  What is left to the host is a ``sum_to_size`` only where the parameter's shape still differs (a
+size-1 dimension inside it, a stride-0 row, a scalar).  The operator's derivative is that of the torch bodies
+``_gumbel_backward`` / ``_bernoulli_backward`` -- which CPU tensors and other dtypes also take inside it -- so a
+method can be differentiated twice (``gradgradcheck``, ``create_graph=True``): in the incoming gradient, which
+RELAX needs, and in the parameters and relaxed samples; the result of that second differentiation is not
+differentiable again.  ``rsample`` alone stays with torch on the host side: its Jacobian is the identity, and
+``sum_to_size`` of the incoming gradient is one launch from C++.  ``threshold`` is computed without gradient, as in
+the reference.  An input with no derivative here (the noise) raises rather than receive a silent zero.
 """
 import abc
+import functools
 import math
 import warnings
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch.distributions import constraints
@@ -228,28 +236,182 @@ def _bernoulli_backward(op: int, g, param, x1, x2):
     return g * ((1 - b) + param.sigmoid() - 2 * s), g * (2 * s - 1), False
 
 
+_BACKWARD = (_gumbel_backward, _bernoulli_backward)
+_HAS_X1_GRAD = (LOG_PROB, CLOG_PROB)  # z of log_prob, zcond of clog_prob
+
+
+def _grad_rows(param: torch.Tensor, expanded: torch.Tensor):
+    """:func:`_param_rows` for the backward: ``expanded`` is ``param`` over the trailing dimensions of the data.
+    Returns (tensor to keep alive, B, p_sr, p_sv, shape) where ``shape`` is what the kernel's (B, V) rows are
+    viewed as, broadcastable to ``param.shape``.  Only a leading dimension the parameter itself has with size 1
+    is left to the sum over the sample rows: one it has with stride 0 (an expanded view handed in as the
+    parameter) gets a gradient per position, read through that stride."""
+    if expanded.dim() == 0:
+        return expanded, 1, 0, 0, ()
+    lead = range(expanded.dim() - 1)
+    kept = [i for i in lead if expanded.size(i) != 1]
+    while kept and param.size(kept[0]) == 1:
+        kept.pop(0)
+    dims = [(expanded.size(i), expanded.stride(i)) for i in kept]
+    if any(a[1] != b[0] * b[1] for a, b in zip(dims, dims[1:])):
+        expanded = expanded.contiguous()
+        dims = [(expanded.size(i), expanded.stride(i)) for i in kept]
+    B = 1
+    for n, _ in dims:
+        B *= n
+    shape = tuple(expanded.size(i) if i in kept else 1 for i in lead) + (expanded.size(-1),)
+    return expanded, B, (dims[-1][1] if dims else 0), expanded.stride(-1), shape
+
+
+def _fresh(t: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    return torch.empty(t.shape, dtype=dtype, device=t.device).copy_(t)
+
+
+@functools.lru_cache(maxsize=256)
+def _workspace_words(code: int, R: int, B: int, V: int) -> int:
+    """float64 words of the parts form's workspace (0: the base form); a pure function of the sizes."""
+    return _cabi.lib().pdt_relaxed_backward_workspace_bytes(code, R, B, V) // 8
+
+
+def _backward_body(family: int, op: int, want: int, g, param, x1, x2):
+    """What ``pydrobert_amd::relaxed_backward`` computes, on tensors that carry no gradient: (the gradient of
+    ``param`` in its own shape, that of ``x1``), ``None`` where ``want`` does not ask.  This is the host's share of
+    every backward (the call is bound by it, not by the kernels), so the common case -- a dense parameter of the
+    data's trailing shape -- takes no view, no row arithmetic and no placeholder."""
+    dtype = x1.dtype
+    if not _on_kernel(param, x1, x2) or g.dtype != dtype or g.device != x1.device:
+        d_param, d_x1, _ = _BACKWARD[family](op, g, param, x1, x2)
+        return (
+            _fresh(d_param.sum_to_size(param.shape), d_param.dtype) if want & 1 else None,
+            _fresh(d_x1, d_x1.dtype) if want & 2 else None,
+        )
+    device = x1.device
+    if x1.numel() == 0:
+        return (
+            torch.zeros(param.shape, dtype=dtype, device=device) if want & 1 else None,
+            torch.empty(x1.shape, dtype=dtype, device=device) if want & 2 else None,
+        )
+    g, x1 = g.contiguous(), x1.contiguous()
+    x2 = None if x2 is None else x2.contiguous()
+    nd = param.dim()
+    if nd and param.shape == x1.shape[x1.dim() - nd:] and param.is_contiguous():
+        V = param.shape[-1]
+        keep, B, p_sr, p_sv, shape = param, param.numel() // V, V, 1, None
+    else:
+        expanded = param.expand(x1.shape[x1.dim() - nd:]) if nd else param
+        V = expanded.shape[-1] if nd else 1
+        keep, B, p_sr, p_sv, shape = _grad_rows(param, expanded)
+    rows = torch.empty(param.shape if shape is None else (B, V), dtype=dtype, device=device) if want & 1 else None
+    d_x1 = torch.empty(x1.shape, dtype=dtype, device=device) if want & 2 else None
+    R = x1.numel() // V
+    code = _DTYPES[dtype]
+    words = _workspace_words(code, R, B, V)
+    ws = torch.empty((words,), dtype=torch.float64, device=device) if words else None
+    lib = _cabi.lib()
+    fn = lib.pdt_relaxed_gumbel_backward if family == GUMBEL else lib.pdt_relaxed_bernoulli_backward
+    with _cabi.on_device(device):
+        rc = fn(
+            op, code, g.data_ptr(), keep.data_ptr(), B, p_sr, p_sv, x1.data_ptr(), _cabi.ptr(x2), R, V,
+            _cabi.ptr(rows), _cabi.ptr(d_x1), _cabi.ptr(ws), _cabi.stream_ptr(device),
+        )  # fmt: skip
+    if rc:
+        _cabi.check(rc, "pdt_relaxed_gumbel_backward" if family == GUMBEL else "pdt_relaxed_bernoulli_backward")
+    if rows is not None and shape is not None:
+        # (a size-1 dimension inside the parameter, a stride-0 row, the dense copy of a broadcast dimension between
+        # others, a scalar: what is left to add up after the kernel's sum over the sample rows)
+        rows = rows.view(shape)
+        rows = rows if rows.shape == param.shape else rows.sum_to_size(param.shape)
+    return rows, d_x1
+
+
+@custom_op("pydrobert_amd::relaxed_backward", mutates_args=())
+def _relaxed_backward_op(
+    family: int, op: int, want: int, g: torch.Tensor, param: torch.Tensor, x1: torch.Tensor, x2: Optional[torch.Tensor]
+) -> Tuple[torch.Tensor, torch.Tensor]:  # fmt: skip
+    """The gradients of method ``op`` of relaxation ``family`` for the gradient ``g`` of its result: (that of
+    ``param``, in ``param``'s own shape, summed over the sample rows; that of ``x1``).  Bit 0 of ``want`` asks for
+    the first and bit 1 for the second; one not asked for comes back empty.  One launch of ``csrc/relaxed.hip``
+    (two where the sample rows are cut into parts) on float32 / float64 ROCm tensors, the torch bodies otherwise."""
+    if op == THRESHOLD or not want & 3 or (want & 2 and op not in _HAS_X1_GRAD):
+        raise RuntimeError("pydrobert_amd::relaxed_backward: method {} has no such derivative".format(op))
+    d_param, d_x1 = _backward_body(
+        family, op, want, g.detach(), param.detach(), x1.detach(), None if x2 is None else x2.detach()
+    )
+    like = d_x1 if d_param is None else d_param
+    return (
+        torch.empty((0,), dtype=like.dtype, device=like.device) if d_param is None else d_param,
+        torch.empty((0,), dtype=like.dtype, device=like.device) if d_x1 is None else d_x1,
+    )
+
+
+@_relaxed_backward_op.register_fake
+def _(family, op, want, g, param, x1, x2):
+    dtype = g.dtype
+    for t in (param, x1, x2):
+        dtype = dtype if t is None else torch.promote_types(dtype, t.dtype)
+    return (
+        param.new_empty(param.shape if want & 1 else (0,), dtype=dtype),
+        x1.new_empty(x1.shape if want & 2 else (0,), dtype=dtype),
+    )
+
+
 def _relaxed_backward(ctx, g):
     param, x1, x2 = ctx.saved_tensors
     if ctx.op == THRESHOLD:
         return None, None, None, None, None
-    fn = _gumbel_backward if ctx.family == GUMBEL else _bernoulli_backward
-    grads = fn(ctx.op, g, param, x1, x2)
-    out = [None, None]
-    for i, (t, d) in enumerate(zip((param, x1, x2), grads)):
-        if not ctx.needs_input_grad[2 + i]:
-            out.append(None)
-        elif d is False or d is None:
+    has = (True, ctx.op in _HAS_X1_GRAD, False)
+    for i in range(3):
+        if ctx.needs_input_grad[2 + i] and not has[i]:
             raise NotImplementedError(
                 "pydrobert_amd::relaxed: method {} has no derivative with respect to its {} argument".format(
                     ctx.op, ("parameter", "first data", "second data")[i]
                 )
             )
-        else:
-            out.append(d.sum_to_size(t.shape) if i == 0 else d)
-    return tuple(out)
+    want = int(ctx.needs_input_grad[2]) | int(ctx.needs_input_grad[3]) << 1
+    if not want:
+        return None, None, None, None, None
+    if ctx.op == RSAMPLE:
+        # the Jacobian is the identity: nothing to compute, and torch's own reduction onto the parameter is one
+        # launch from C++ (5 us a call against the 12 us and more of any launch through this layer: DESIGN.md 4.11)
+        return None, None, g.sum_to_size(param.shape), None, None
+    if _cabi.plain_call(g, param, x1, x2):  # (an ordinary backward: nothing to record, nothing for the dispatcher)
+        d_param, d_x1 = _backward_body(ctx.family, ctx.op, want, g, param, x1, x2)
+    else:
+        d_param, d_x1 = torch.ops.pydrobert_amd.relaxed_backward(ctx.family, ctx.op, want, g, param, x1, x2)
+    return None, None, d_param if want & 1 else None, d_x1 if want & 2 else None, None
 
 
 register_autograd("pydrobert_amd::relaxed", _relaxed_backward, setup_context=_relaxed_setup_context)
+
+
+def _backward_setup_context(ctx, inputs, output):
+    ctx.family, ctx.op, ctx.want = inputs[:3]
+    ctx.save_for_backward(*inputs[3:])
+
+
+def _backward_backward(ctx, gg_param, gg_x1):
+    """The derivative of the backward operator: the torch body's, in differentiable torch operations."""
+    g, param, x1, x2 = ctx.saved_tensors
+    with torch.enable_grad():
+        leaves = [t.detach().requires_grad_() for t in (g, param, x1)]
+        d_param, d_x1, _ = _BACKWARD[ctx.family](ctx.op, *leaves, x2)
+        outs, gouts = [], []
+        if ctx.want & 1 and gg_param is not None:
+            outs.append(d_param.sum_to_size(param.shape))
+            gouts.append(gg_param)
+        if ctx.want & 2 and gg_x1 is not None:
+            outs.append(d_x1)
+            gouts.append(gg_x1)
+        targets = [t for i, t in enumerate(leaves) if ctx.needs_input_grad[3 + i]]
+        live = [(d, gd) for d, gd in zip(outs, gouts) if d.requires_grad]
+        second = iter(
+            torch.autograd.grad([d for d, _ in live], targets, [gd for _, gd in live], allow_unused=True)
+            if live and targets else [None] * len(targets)
+        )  # fmt: skip
+    return (None, None, None) + tuple(next(second) if ctx.needs_input_grad[3 + i] else None for i in range(3)) + (None,)
+
+
+register_autograd("pydrobert_amd::relaxed_backward", _backward_backward, setup_context=_backward_setup_context)
 
 
 def _relaxed(family: int, op: int, param, x1, x2=None) -> torch.Tensor:

@@ -382,6 +382,20 @@ int pdt_beam_search_table(const float *table, int64_t tb_sr, int64_t tb_sv, int6
                           int64_t *lens_out, int32_t *finish, int32_t *t_stop, void *stream);
 int pdt_beam_search_table_paths(const uint32_t *trie, const int32_t *finish, int64_t N, int64_t n_iters,
                                 int64_t width, int64_t T, int64_t pad_value, int64_t *y, void *stream);
+/* Host only, no device work: what the launchers decide from the sizes (they call these themselves).
+ *   pdt_beam_search_table_plan: the instance of the one-launch search for a (U, V) table with token stride
+ *   tb_sv -- 0 a wave owns whole rows (width <= 16 and V <= 1024), 1 chunks numbered across the rows;
+ *   PDT_E_UNSUPPORTED where pdt_beam_search_table returns it, PDT_E_ARG for sizes below 1.
+ *   pdt_beam_search_step_plan: the kernel of one iteration (pdt_beam_search_step: has_rows = 0;
+ *   pdt_beam_search_step_table with row_stats: has_rows = 1; sc_sv the token stride) -- 0 the sorted list
+ *   per prefix, with the waves per batch element (the power of two <= min(Kp, 8)) written to *waves when
+ *   it is not NULL; 1 one selection over all Kp * V candidates (table rows of more than 64 tokens at stride
+ *   1 with Kp * ceil(V / 64) <= 256); PDT_E_ARG / PDT_E_TOO_LONG where the entry points refuse the sizes
+ *   (Kp or width above 64).  The run-time switch PDT_STEP_FLAT=0 sends the shapes of form 1 to form 0; the
+ *   plan reports the shape's answer with the switch on. */
+int pdt_beam_search_table_plan(int64_t U, int64_t V, int64_t width, int64_t tb_sv);
+int pdt_beam_search_step_plan(int64_t Kp, int64_t V, int64_t width, int has_rows, int64_t sc_sv,
+                              int32_t *waves);
 
 /* ---------------------------------------------------------------------------------------
  * The whole CTCPrefixSearch with a LookupLanguageModel in the loop (_decoding.py:1083-1202 with

@@ -212,13 +212,15 @@ __global__ void __launch_bounds__(64 * kStepFlatWaves, ROWS16 ? PDT_BS_WAVES : 6
       int new_src = (int)(idx_of(tk) >> 20), new_tok = (int)(idx_of(tk) & 0xfffffu);
       float new_lp = fkey_inv(key_of(tk));
       if (have < K && count <= PDT_SURV_CAP) {
-        // fewer than K finite candidates: -inf ones of the paths that have not ended, in flat order, behind them
+        // fewer than K finite candidates: the -inf ones, in flat order, behind them (of an ended path: every
+        // token but eos -- eos too when the path's own score is -inf)
         const int filled = have;
         for (int k = 0; k < Kp && have < K; ++k) {
-          if ((ended_mask >> k) & 1ull) continue;
+          const bool ended_k = (ended_mask >> k) & 1ull;
+          const bool eos_too = ended_k && st_lp[k] == -PDT_INF;
           for (int v0 = 0; v0 < V && have < K; v0 += PDT_WAVE) {
             const int v = v0 + lane;
-            const bool is = v < V && value_at(k, v) == -PDT_INF;
+            const bool is = v < V && (ended_k ? (v != eos || eos_too) : value_at(k, v) == -PDT_INF);
             const u64 b = __ballot(is);
             const int rank = have + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
             if (is && rank < K) {
@@ -245,7 +247,9 @@ __global__ void __launch_bounds__(64 * kStepFlatWaves, ROWS16 ? PDT_BS_WAVES : 6
       if (lane < W) {
         st_lp[lane] = valid ? new_lp : -PDT_INF;  // :145-153 for the overflow
         st_len[lane] = valid ? src_len + grew : 0;
-        st_tok[lane] = valid ? new_tok : 0;
+        // the token at the path's end: an ended source's entry stays ended whatever it took (its length does
+        // not grow, so its last token is still eos -- the -inf candidates a beam wider than its finite ones takes)
+        st_tok[lane] = valid ? (grew ? new_tok : eos) : 0;
         st_row[lane] = valid ? new_tok : 0;  // the next row of the table: the path's last token
         a.trie[(n * a.n_iters + t) * W + lane] = valid ? ((unsigned)src << 20) | (unsigned)new_tok : 0u;
       }
@@ -334,6 +338,17 @@ int pdt_row_log_softmax_stats(const float *table, int64_t tb_sr, int64_t tb_sv, 
   return (int)hipGetLastError();
 }
 
+// Which instance of beam_search_table_kernel serves these sizes (host arithmetic only; the launcher asks
+// it): 0 ROWS16 (width <= 16, V <= 1024), 1 the chunk-numbered form, PDT_E_UNSUPPORTED where neither does.
+int pdt_beam_search_table_plan(int64_t U, int64_t V, int64_t width, int64_t tb_sv) {
+  using namespace pdt;
+  if (U < 1 || V < 1 || width < 1) return PDT_E_ARG;
+  if (tb_sv != 1 || V <= PDT_WAVE || V >= (1 << 20) || V > U || width > PDT_WAVE ||
+      width * ((V + PDT_WAVE - 1) / PDT_WAVE) > kStepFlatWaves * kStepFlatRegs)
+    return PDT_E_UNSUPPORTED;
+  return width <= 16 && V <= 16 * PDT_WAVE ? 0 : 1;
+}
+
 int pdt_beam_search_table(const float *table, int64_t tb_sr, int64_t tb_sv, int64_t U, const float *row_stats,
                                      int64_t sos_row, int64_t N, int64_t V, int64_t width, int64_t n_iters, int has_eos,
                                      int64_t eos, int finish_all_paths, uint32_t *trie, float *log_probs_out,
@@ -344,15 +359,14 @@ int pdt_beam_search_table(const float *table, int64_t tb_sr, int64_t tb_sv, int6
   if (!table || !row_stats || !trie || !log_probs_out || !lens_out || !finish || !t_stop) return PDT_E_ARG;
   if (has_eos && (eos < 0 || eos >= V)) return PDT_E_ARG;
   if (N >= (1ll << 31) || n_iters >= (1 << 24)) return PDT_E_TOO_LONG;
-  if (tb_sv != 1 || V <= PDT_WAVE || V >= (1 << 20) || V > U || width > PDT_WAVE ||
-      width * ((V + PDT_WAVE - 1) / PDT_WAVE) > kStepFlatWaves * kStepFlatRegs)
-    return PDT_E_UNSUPPORTED;  // (the per-iteration entry points serve those)
+  const int form = pdt_beam_search_table_plan(U, V, width, tb_sv);
+  if (form < 0) return form;  // (PDT_E_UNSUPPORTED: the per-iteration entry points serve those)
   BeamSearchArgs a{};
   a.table = table; a.tb_sr = tb_sr; a.row_stats = row_stats;
   a.N = (int)N; a.V = (int)V; a.W = (int)width; a.n_iters = (int)n_iters; a.sos_row = (int)sos_row;
   a.has_eos = has_eos; a.finish_all = finish_all_paths; a.eos = (int)eos;
   a.trie = trie; a.lp_out = log_probs_out; a.lens_out = lens_out; a.finish = finish; a.t_stop = t_stop;
-  if (width <= 16 && V <= 16 * PDT_WAVE)
+  if (form == 0)
     hipLaunchKernelGGL(beam_search_table_kernel<true>, dim3((unsigned)N), dim3(64 * kStepFlatWaves), 0, (hipStream_t)stream, a);
   else
     hipLaunchKernelGGL(beam_search_table_kernel<false>, dim3((unsigned)N), dim3(64 * kStepFlatWaves), 0, (hipStream_t)stream, a);

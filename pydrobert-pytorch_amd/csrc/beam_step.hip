@@ -108,11 +108,16 @@ __global__ void __launch_bounds__(512) beam_step_kernel(const BeamStepArgs a) {
   for (int k = wave; k < Kp; k += NW) {
     const float bias = a.lpp[n * a.lp_sn + k * a.lp_sk];
     if (ended[k]) {
-      if (lane == 0) {
-        tl[k * PDT_WAVE] = (int)a.eos;
-        tlm[k * PDT_WAVE] = (bias + 0.0f) + 0.0f;
-        cnt[k] = 1;
+      // eos first, then the other tokens in order: they are candidates without a score (-inf, :448-458), which
+      // a beam wider than its finite candidates takes in flat order like any other (an ended path whose own
+      // score is -inf offers nothing but ties: token order)
+      if (lane < M) {
+        const int e = (int)a.eos;
+        const bool plain = bias == -PDT_INF;
+        tl[k * PDT_WAVE + lane] = plain ? lane : (lane == 0 ? e : (lane - 1 < e ? lane - 1 : lane));
+        tlm[k * PDT_WAVE + lane] = lane == 0 && !plain ? (bias + 0.0f) + 0.0f : -PDT_INF;
       }
+      if (lane == 0) cnt[k] = M;
     } else {
       const int64_t r = a.rows ? a.rows[n * Kp + k] : 0;
       const float *row = a.rows ? a.scores + r * a.sc_sk : a.scores + n * a.sc_sn + k * a.sc_sk;
@@ -203,7 +208,8 @@ __global__ void __launch_bounds__(512) beam_step_kernel(const BeamStepArgs a) {
 //   2. every wave appends its candidates >= tau to one survivor list (LDS cursor);
 //   3. wave 0 sorts them by (value, lowest k * V + v first): lane i holds winner i.
 // tau = -inf (fewer than K columns with a finite maximum: most paths ended): the survivors are the finite
-// candidates, -inf ones of paths that have not ended fill up in flat order.  A survivor list that overflows:
+// candidates, the -inf ones (an ended path's tokens other than eos among them) fill up in flat order, as the
+// reference's candidate table holds them (ties: lowest flat index).  A survivor list that overflows:
 // every candidate again, from memory, through the chunked top-64 merge.  Same results as the list form.
 __global__ void __launch_bounds__(64 * kStepFlatWaves, 6) beam_step_flat_kernel(const BeamStepArgs a) {
   __shared__ unsigned colmax[kStepFlatWaves * PDT_WAVE];
@@ -367,14 +373,15 @@ __global__ void __launch_bounds__(64 * kStepFlatWaves, 6) beam_step_flat_kernel(
     int new_src = (int)(idx_of(tk) >> 20), new_tok = (int)(idx_of(tk) & 0xfffffu);
     float new_lp = fkey_inv(key_of(tk));
     if (have < K && count <= PDT_SURV_CAP) {
-      // tau = -inf and fewer than K finite candidates: -inf candidates of the paths that have not ended, in
-      // flat order, behind them
+      // tau = -inf and fewer than K finite candidates: the -inf candidates, in flat order, behind them (of an
+      // ended path: every token but eos, :448-458 -- eos too when the path's own score is -inf)
       const int filled = have;
       for (int k = 0; k < Kp && have < K; ++k) {
-        if ((ended_mask >> k) & 1ull) continue;
+        const bool ended_k = (ended_mask >> k) & 1ull;
+        const bool eos_too = ended_k && a.lpp[n * a.lp_sn + k * a.lp_sk] == -PDT_INF;
         for (int v0 = 0; v0 < V && have < K; v0 += PDT_WAVE) {
           const int v = v0 + lane;
-          const bool is = v < V && value_at(k, v) == -PDT_INF;
+          const bool is = v < V && (ended_k ? (v != eos || eos_too) : value_at(k, v) == -PDT_INF);
           const u64 b = __ballot(is);
           const int rank = have + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
           if (is && rank < K) {  // winner number `rank`: handed to lane `rank`
@@ -437,7 +444,9 @@ static int beam_step_entry(const float *scores, int64_t sc_sn, int64_t sc_sk, in
     return PDT_E_ARG;
   if (has_eos && (eos < 0 || eos >= V)) return PDT_E_ARG;
   if (sizes != PDT_OK) return sizes;
-  if (width > PDT_WAVE || Kp > PDT_WAVE) return PDT_E_TOO_LONG;  // (wider beams: the step-by-step form)
+  int nw = 0;
+  const int form = pdt_beam_search_step_plan(Kp, V, width, rows && row_stats, sc_sv, &nw);
+  if (form < 0) return form;  // (wider beams: the step-by-step form)
   BeamStepArgs a{};
   a.scores = scores; a.sc_sn = sc_sn; a.sc_sk = sc_sk; a.sc_sv = sc_sv;
   a.rows = rows; a.row_stats = row_stats;
@@ -449,12 +458,10 @@ static int beam_step_entry(const float *scores, int64_t sc_sn, int64_t sc_sk, in
   a.pad_clamped = pad_value < 0 ? 0 : (pad_value > V - 1 ? V - 1 : pad_value);
   a.y_next = y_next; a.y_next_lens = y_next_lens; a.lp_next = log_probs_next; a.next_src = next_src;
   a.active = active; a.pad_from = pad_from;
-  if (switches().step_flat != 0 && rows && row_stats && sc_sv == 1 && V > PDT_WAVE && V < (1 << 20) &&
-      Kp * ((V + PDT_WAVE - 1) / PDT_WAVE) <= kStepFlatWaves * kStepFlatRegs) {
+  if (form == 1 && switches().step_flat != 0) {
     hipLaunchKernelGGL(beam_step_flat_kernel, dim3((unsigned)a.N), dim3(64 * kStepFlatWaves), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
   }
-  const int nw = step_waves(a.Kp);
   a.waves_per_wg = nw;
   const size_t smem = step_list_lds(nw, a.Kp, a.W, 8);  // + the ended flag and the list length of every prefix
   hipLaunchKernelGGL(beam_step_kernel, dim3((unsigned)a.N), dim3(64 * nw), smem, (hipStream_t)stream, a);
@@ -462,6 +469,23 @@ static int beam_step_entry(const float *scores, int64_t sc_sn, int64_t sc_sk, in
 }
 
 }  // namespace pdt
+
+// Which kernel serves an iteration of these sizes (host arithmetic only; beam_step_entry asks it): 1 the
+// flat form -- table rows with their statistics, token stride 1, rows of more than 64 tokens, and the
+// K' * ceil(V / 64) chunks fit the registers of eight waves --, else 0 the list form with *waves waves per
+// element.  PDT_STEP_FLAT=0 sends the flat shapes to the list form at run time; the plan does not look at it.
+extern "C" int pdt_beam_search_step_plan(int64_t Kp, int64_t V, int64_t width, int has_rows, int64_t sc_sv,
+                                         int32_t *waves) {
+  using namespace pdt;
+  const int sizes = step_sizes_ok(0, Kp, V, width, 0);
+  if (sizes != PDT_OK) return sizes;
+  if (width > PDT_WAVE || Kp > PDT_WAVE) return PDT_E_TOO_LONG;
+  if (waves) *waves = step_waves((int)Kp);
+  if (has_rows && sc_sv == 1 && V > PDT_WAVE && V < (1 << 20) &&
+      Kp * ((V + PDT_WAVE - 1) / PDT_WAVE) <= kStepFlatWaves * kStepFlatRegs)
+    return 1;
+  return 0;
+}
 
 extern "C" int pdt_beam_search_step(const float *scores, int64_t sc_sn, int64_t sc_sk, int64_t sc_sv, int64_t N,
                                     int64_t Kp, int64_t V, int64_t width, const float *log_probs_prev,

@@ -25,7 +25,8 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # existing declaration changed), and so were those of the estimators (pdt_mc_reduce*, pdt_imh_chain) and the
 # host-only plans of the searches with an n-gram model (pdt_ctc_lm_table_search_plan,
 # pdt_ctc_lookup_lm_search_lds_bytes) and the backward of relaxed sampling (pdt_relaxed_backward_parts,
-# pdt_relaxed_backward_workspace_bytes, pdt_relaxed_gumbel_backward, pdt_relaxed_bernoulli_backward).
+# pdt_relaxed_backward_workspace_bytes, pdt_relaxed_gumbel_backward, pdt_relaxed_bernoulli_backward) and the
+# host-only plans of BeamSearch's kernels (pdt_beam_search_step_plan, pdt_beam_search_table_plan).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -94,6 +95,8 @@ SIGNATURES = {
         [_P, _I64, _I64, _I64, _P, _I64, _I64, _I64, _I64, _I64, _INT, _I64, _INT, _P, _P, _P, _P, _P, _P],
     ),
     "pdt_beam_search_table_paths": (_INT, [_P, _P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
+    "pdt_beam_search_table_plan": (_INT, [_I64, _I64, _I64, _I64]),
+    "pdt_beam_search_step_plan": (_INT, [_I64, _I64, _I64, _INT, _I64, _P]),
     "pdt_lens_reach": (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _P, _P]),
     "pdt_beam_search_advance": (
         _INT,

@@ -28,6 +28,22 @@ class BigramLM(MixableSequentialLanguageModel):
         return prev_true
 
 
+class StartRowBigramLM(BigramLM):
+    """A bigram table whose batch elements start from rows of their own: at index 0 -- one empty prefix per
+    element, so flattened row b is element b -- element n reads row ``starts[n]``, afterwards every prefix
+    reads the row of its last token.  No state.  (The numpy twin is tests/_beam_forms.py's StartRowLM.)"""
+
+    def __init__(self, table, starts):
+        super().__init__(table)
+        self.register_buffer("starts", starts)
+
+    def calc_idx_log_probs(self, hist, prev, idx):
+        if hist.shape[0] == 0 or int(idx.max()) == 0:
+            assert hist.shape[1] == self.starts.shape[0]
+            return self.table[self.starts], prev
+        return super().calc_idx_log_probs(hist, prev, idx)
+
+
 from typing import Dict, Tuple  # noqa: E402
 
 

@@ -1161,7 +1161,9 @@ def test_beam_search_fused_iterations_equal_the_step_by_step_loop(device, finish
     """BeamSearch with every iteration in one kernel (csrc/beam_step.hip; the number of unfinished
     batch elements read every eighth iteration) against the loop of reference-shaped torch ops around
     beam_search_advance (PDT_BEAM_FUSED=0): same paths, lengths and padding, log-probabilities to 1e-5;
-    searches that end by eos at iterations that are no multiple of eight, by max_iters, at once."""
+    searches that end by eos at iterations that are no multiple of eight, by max_iters, at once.  The
+    model has no state, so the batch elements of one search are copies of each other and finish at the
+    same iteration; elements that finish apart are tests/test_beam_forms_gpu.py's mixed batches."""
     from _toy_lm import BigramLM
 
     class PositionalBigramLM(BigramLM):

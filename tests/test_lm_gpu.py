@@ -250,8 +250,10 @@ def test_beam_search_every_iteration_in_one_launch(switch):
     LDS, a (source, token) word per entry and iteration in a trie, the paths read off it at the end -- against
     the iteration-per-launch table route: the same `y` (rows beyond the lengths and the padding included),
     lengths and log-probabilities, to the bit.  Rows of 65 .. 1024 tokens with beams up to 16 take the
-    rows-per-wave form, wider beams and longer rows the chunk-numbered one; eos biased so that batch elements
-    finish at different iterations (and some never do)."""
+    rows-per-wave form, wider beams and longer rows the chunk-numbered one; eos biased so that the searches
+    end at different iterations from case to case (and some never do).  The model has no state and every
+    batch element starts from the same context, so the elements of ONE search are copies of each other and
+    finish together: batches whose elements finish apart are tests/test_beam_forms_gpu.py's."""
     rng = np.random.default_rng(5150)
     switch("PDT_BEAM_FUSED", "1")
     switch("PDT_BEAM_TABLE", "1")

@@ -166,6 +166,7 @@ int pdt_oc_expand(const uint32_t *bitmask, const int64_t *class_tokens, int64_t 
  * logits (H, N, V) float32 through element strides; weight (V,) or NULL.
  * Backward: grad_logits (H, N, V) contiguous from grad_loss (H, N).
  * status (optional) bit 0 is set when a target lies outside [0, V).
+ * PDT_E_TOO_LONG: V >= 2^30, H, N or R above 2^31 - 1 (ints in the kernel), H * N >= 2^33.
  * ------------------------------------------------------------------------------------- */
 int pdt_ocd_loss_forward(const float *logits, int64_t H, int64_t N, int64_t V, int64_t lg_sh,
                          int64_t lg_sn, int64_t lg_sv, const uint32_t *bitmask,
@@ -513,6 +514,8 @@ int pdt_random_walk_table(const float *table, int64_t tb_sr, int64_t R, int64_t 
  * step axis, logits (A, S, B, V) contiguous; out (A, B) = sum over valid steps of
  * log_softmax(logits)[hyp]; tokens outside [0, V) and steps after the first eos are skipped.
  * Backward: grad_logits (same layout) from grad_out (A, B).
+ * PDT_E_TOO_LONG: V >= 2^30 (all three; V is an int in the kernels), T beyond the LDS of the greedy
+ * search (more than 20 480 frames), N, A, S, B or A * B >= 2^31.
  * ------------------------------------------------------------------------------------- */
 int pdt_ctc_greedy_search(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
                           int64_t lg_sn, int64_t lg_sv, const int64_t *in_lens, int64_t blank_idx,
@@ -692,6 +695,7 @@ int pdt_lookup_lm_log_probs(const int64_t *hist, int64_t S, int64_t B, int64_t h
  *   valid_mixture == 0: out = nonext * exp(beta * log_softmax(lm_log_probs))        (shallow fusion)
  *   valid_mixture != 0: out = (1 - beta) * nonext + beta * softmax(lm_log_probs) * (1 - blank)
  *   out (N, Kp, V) float32 contiguous.  No gradient (the differentiable path composes torch ops).
+ *   PDT_E_TOO_LONG: V >= 2^30, Kp above 2^31 - 1, N * Kp >= 2^33 (pdt_lm_factor_table: V, rows >= 2^33).
  * ------------------------------------------------------------------------------------- */
 int pdt_fusion_ext(const float *lm_log_probs, int64_t N, int64_t Kp, int64_t V, const float *nonext,
                    int64_t ne_sn, int64_t ne_sv, const float *blank, int64_t bl_sn, float beta,
@@ -708,6 +712,8 @@ int pdt_fusion_ext(const float *lm_log_probs, int64_t N, int64_t Kp, int64_t V, 
  * pad < lens), 2 replicate (x[n, 0], x[n, lens - 1]; the caller checks lens >= 1).
  * pdt_pad_variable_backward: the adjoint with respect to x, written as a gather (deterministic),
  * dtype 0 float32 / 1 float64; grad_out (N, Tp, F), grad_x (N, T, F) of that type.
+ * PDT_E_TOO_LONG: an output (backward: grad_x) of 2^32 - 4096 elements or more -- elements are numbered
+ * with 32 bits -- or N, T, F or Tp above 2^31 - 1; the same for pdt_gather_steps and pdt_chunk_by_slices.
  * ------------------------------------------------------------------------------------- */
 int pdt_pad_variable(const void *x, int64_t N, int64_t T, int64_t F, int64_t elem_bytes,
                      const int64_t *lens, const int64_t *pad, int mode, const void *fill,

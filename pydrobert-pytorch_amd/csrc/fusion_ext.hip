@@ -93,7 +93,7 @@ extern "C" int pdt_lm_factor_table(const float *lm_log_probs, int64_t rows, int6
   if (rows < 0 || V < 1 || out_stride < V) return PDT_E_ARG;
   if (rows == 0) return PDT_OK;
   if (!lm_log_probs || !out) return PDT_E_ARG;
-  if (rows >= (1ll << 31) * 4 || V >= (1ll << 31)) return PDT_E_TOO_LONG;
+  if (rows >= (1ll << 31) * 4 || V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel
   auto kern = V <= 8 * PDT_WAVE ? lm_factor_kernel<8> : lm_factor_kernel<16>;
   hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, lm_log_probs, rows,
                      (int)V, beta, valid_mixture, out, out_stride);
@@ -108,7 +108,8 @@ extern "C" int pdt_fusion_ext(const float *lm_log_probs, int64_t N, int64_t Kp, 
   if (N == 0) return PDT_OK;
   if (!lm_log_probs || !nonext || !out || (valid_mixture && !blank)) return PDT_E_ARG;
   const int64_t rows = N * Kp;
-  if (rows >= (1ll << 31) * 4 || V >= (1ll << 31)) return PDT_E_TOO_LONG;
+  // Kp and V are ints in the kernel
+  if (rows >= (1ll << 31) * 4 || V >= (1 << 30) || Kp > 0x7fffffffll) return PDT_E_TOO_LONG;
   FusionArgs a{lm_log_probs, nonext, ne_sn, ne_sv, blank, bl_sn, rows, (int)Kp, (int)V, valid_mixture, beta, out};
   auto kern = V <= 8 * PDT_WAVE ? fusion_ext_kernel<8> : fusion_ext_kernel<16>;
   hipLaunchKernelGGL(kern, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);

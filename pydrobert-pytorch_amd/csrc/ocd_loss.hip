@@ -165,7 +165,8 @@ int pdt_ocd_loss_forward(const float *logits, int64_t H, int64_t N, int64_t V, i
                          void *stream) {
   using namespace pdt;
   if (H < 0 || N < 0 || V < 1 || R < 0) return PDT_E_ARG;
-  if (V >= (1ll << 31)) return PDT_E_TOO_LONG;  // V is an int in the kernel, forward and backward alike
+  // H, N, V and R are ints in the kernel, forward and backward alike; a row is walked in 64-token steps
+  if (V >= (1 << 30) || H > 0x7fffffffll || N > 0x7fffffffll || R > 0x7fffffffll) return PDT_E_TOO_LONG;
   if (H == 0 || N == 0) return PDT_OK;
   if (!logits || !bitmask || !class_tokens || !loss || !count) return PDT_E_ARG;
   if (H * N >= (1ll << 31) * 4) return PDT_E_TOO_LONG;
@@ -184,7 +185,8 @@ int pdt_ocd_loss_backward(const float *logits, int64_t H, int64_t N, int64_t V, 
                           void *stream) {
   using namespace pdt;
   if (H < 0 || N < 0 || V < 1 || R < 0) return PDT_E_ARG;
-  if (V >= (1ll << 31)) return PDT_E_TOO_LONG;  // V is an int in the kernel, forward and backward alike
+  // H, N, V and R are ints in the kernel, forward and backward alike; a row is walked in 64-token steps
+  if (V >= (1 << 30) || H > 0x7fffffffll || N > 0x7fffffffll || R > 0x7fffffffll) return PDT_E_TOO_LONG;
   if (H == 0 || N == 0) return PDT_OK;
   if (!logits || !bitmask || !class_tokens || !grad_loss || !grad_logits) return PDT_E_ARG;
   if (H * N >= (1ll << 31) * 4) return PDT_E_TOO_LONG;

@@ -108,6 +108,7 @@ int pdt_pad_variable(const void *x, int64_t N, int64_t T, int64_t F, int64_t ele
   if (N < 0 || T < 0 || F < 0 || Tp < 0 || mode < 0 || mode > 2) return PDT_E_ARG;
   if (N == 0 || Tp == 0 || F == 0) return PDT_OK;
   if (!lens || !pad || !fill || !out || (T > 0 && !x)) return PDT_E_ARG;
+  if (N > 0x7fffffffll || T > 0x7fffffffll || F > 0x7fffffffll || Tp > 0x7fffffffll) return PDT_E_TOO_LONG;  // ints in PadArgs
   if (N * Tp * F >= (1ll << 32) - 1024 * kPerThread) return PDT_E_TOO_LONG;
   PadArgs a{};
   a.x = x; a.lens = lens; a.pad = pad; a.N = (int)N; a.T = (int)T; a.F = (int)F; a.Tp = (int)Tp;
@@ -132,6 +133,7 @@ int pdt_pad_variable_backward(const void *grad_out, int dtype, int64_t N, int64_
   if (N < 0 || T < 0 || F < 0 || Tp < 0 || mode < 0 || mode > 2 || dtype < 0 || dtype > 1) return PDT_E_ARG;
   if (N == 0 || T == 0 || F == 0) return PDT_OK;
   if (!grad_out || !lens || !pad || !grad_x) return PDT_E_ARG;
+  if (N > 0x7fffffffll || T > 0x7fffffffll || F > 0x7fffffffll || Tp > 0x7fffffffll) return PDT_E_TOO_LONG;  // ints in PadArgs
   if (N * T * F >= (1ll << 32) - 1024 * kPerThread) return PDT_E_TOO_LONG;
   PadArgs a{};
   a.lens = lens; a.pad = pad; a.N = (int)N; a.T = (int)T; a.F = (int)F; a.Tp = (int)Tp;

@@ -353,6 +353,8 @@ chunk_stats_kernel(const int64_t *__restrict__ slices, const int64_t *__restrict
 }
 
 static bool fits32(int64_t elems) { return elems < (1ll << 32) - 1024 * kPerThread; }
+// sizes the argument blocks keep as int
+static bool fits_int(int64_t a, int64_t b, int64_t c, int64_t d) { return (a | b | c | d) <= 0x7fffffffll; }
 
 }  // namespace pdt
 
@@ -378,6 +380,7 @@ int pdt_gather_steps(const void *x, int64_t N, int64_t T, int64_t F, int64_t ele
   if (N < 0 || T < 0 || F < 0 || To < 0) return PDT_E_ARG;
   if (N == 0 || To == 0 || F == 0) return PDT_OK;
   if (!map || !fill || !out || (T > 0 && !x)) return PDT_E_ARG;
+  if (!fits_int(N, T, F, To)) return PDT_E_TOO_LONG;
   if (!fits32(N * To * F)) return PDT_E_TOO_LONG;
   CopyArgs a{};
   a.x = x; a.out = out; a.fill = fill; a.x_sn = x_sn; a.x_st = x_st;
@@ -393,6 +396,7 @@ int pdt_chunk_by_slices(const void *x, int64_t N, int64_t T, int64_t F, int64_t 
   if (N < 0 || T < 0 || F < 0 || Tp < 0 || mode < 0 || mode > 2) return PDT_E_ARG;
   if (N == 0 || Tp == 0 || F == 0) return PDT_OK;
   if (!slices || !fill || !out || (T > 0 && !x)) return PDT_E_ARG;
+  if (!fits_int(N, T, F, Tp)) return PDT_E_TOO_LONG;
   if (!fits32(N * Tp * F)) return PDT_E_TOO_LONG;
   CopyArgs a{};
   a.x = x; a.out = out; a.fill = fill; a.x_sn = x_sn; a.x_st = x_st;
@@ -420,6 +424,7 @@ int pdt_chunk_by_slices_backward(const void *grad_out, int dtype, int64_t N, int
   if (N < 0 || T < 0 || F < 0 || Tp < 0 || mode < 0 || mode > 2 || dtype < 0 || dtype > 1) return PDT_E_ARG;
   if (N == 0 || T == 0 || F == 0) return PDT_OK;
   if (!slices || !grad_x || (Tp > 0 && !grad_out)) return PDT_E_ARG;
+  if (!fits_int(N, T, F, Tp)) return PDT_E_TOO_LONG;
   if (!fits32(N * T * F) || !fits32(N * Tp * F)) return PDT_E_TOO_LONG;
   const unsigned total = (unsigned)(N * T * F);
   const dim3 grid((total + 256 * kPerThread - 1) / (256 * kPerThread));
@@ -494,7 +499,7 @@ int pdt_slice_ali_emit(const int32_t *seg, int64_t N, int64_t T, const int64_t *
   if (N < 0 || T < 0 || left < 0 || right < 0) return PDT_E_ARG;
   if (N == 0 || T == 0) return PDT_OK;
   if (!seg || !nseg || !cnt || !base || !slices || !sources) return PDT_E_ARG;
-  if (!fits32(N * T)) return PDT_E_TOO_LONG;
+  if (!fits_int(N, T, 0, 0) || !fits32(N * T)) return PDT_E_TOO_LONG;
   const unsigned total = (unsigned)(N * T);
   hipLaunchKernelGGL(ali_emit_kernel, dim3((total + 255) / 256), dim3(256), 0, (hipStream_t)stream, seg, in_lens,
                      nseg, cnt, (int)T, left, right, valid_only, SliceOut{slices, sources, base, T}, total);

@@ -204,6 +204,7 @@ int pdt_ctc_greedy_search(const float *logits, int64_t T, int64_t N, int64_t V, 
   const size_t smem = ((size_t)(T > 0 ? T : 1) * 8 + 15) & ~(size_t)15;  // arg-max + value per frame
   if (smem > 160 * 1024) return PDT_E_TOO_LONG;
   if (N > 0x7fffffffll) return PDT_E_TOO_LONG;
+  if (V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel (row_reduce.hpp walks it in 64-token steps)
   GreedyArgs a{};
   a.logits = logits; a.lg_st = lg_st; a.lg_sn = lg_sn; a.lg_sv = lg_sv;
   a.in_lens = in_lens; a.T = (int)T; a.N = (int)N; a.V = (int)V; a.blank = (int)blank_idx;
@@ -223,6 +224,7 @@ int pdt_sequence_log_probs_forward(const float *logits, const int64_t *hyp, int6
   if (A * B == 0) return PDT_OK;
   if ((S > 0 && (!logits || !hyp)) || !out) return PDT_E_ARG;
   if (A * B >= (1ll << 31) || A >= (1ll << 31) || S >= (1ll << 31) || B >= (1ll << 31)) return PDT_E_TOO_LONG;
+  if (V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel
   SlpArgs a{};
   a.logits = logits; a.hyp = hyp; a.A = (int)A; a.S = (int)S; a.B = (int)B; a.V = (int)V;
   a.has_eos = has_eos; a.eos = eos; a.out = out; a.nw = seq_waves(S);
@@ -239,6 +241,7 @@ int pdt_sequence_log_probs_backward(const float *logits, const int64_t *hyp, int
   if (A * S * B == 0) return PDT_OK;
   if (!logits || !hyp || !grad_out || !grad_logits) return PDT_E_ARG;
   if (A * B >= (1ll << 31) || A >= (1ll << 31) || S >= (1ll << 31) || B >= (1ll << 31)) return PDT_E_TOO_LONG;
+  if (V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel
   SlpArgs a{};
   a.logits = logits; a.hyp = hyp; a.A = (int)A; a.S = (int)S; a.B = (int)B; a.V = (int)V;
   a.has_eos = has_eos; a.eos = eos; a.grad_out = grad_out; a.grad_logits = grad_logits; a.nw = seq_waves(S);

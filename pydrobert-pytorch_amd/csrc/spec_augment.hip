@@ -433,7 +433,7 @@ static bool spec_aug_args(pdt::SpecAugArgs &a, int *rc, std::initializer_list<co
     if (!p) return false;
   if ((MT > 0 && (!t_0 || !t_len)) || (MF > 0 && (!f_0 || !f_len))) return false;
   *rc = PDT_E_TOO_LONG;
-  if (T * F >= (1ll << 31)) return false;
+  if (T * F >= (1ll << 31) || N > 0x7fffffffll || MT > 0x7fffffffll || MF > 0x7fffffffll) return false;  // ints below
   a.t0 = t_0; a.tl = t_len; a.f0 = f_0; a.fl = f_len;
   a.N = (int)N; a.T = (int)T; a.F = (int)F; a.MT = (int)MT; a.MF = (int)MF;
   *rc = PDT_OK;

@@ -566,10 +566,10 @@ def _ocd_loss_rows_op(
             raise RuntimeError("If include_eos=True, eos ({}) must be a class idx".format(eos))
         if eos is not None and eos == ignore_index:
             raise RuntimeError("If include_eos=True, eos cannot equal ignore_index ({}".format(eos))
-    if logits.size(-1) >= 2**31:  # the one bound on V, forward and backward alike (csrc/ocd_loss.hip)
+    if logits.size(-1) >= 2**30:  # the one bound on V, forward and backward alike (csrc/ocd_loss.hip)
         raise RuntimeError(
             "logits has V = {} classes; the MI355X kernels index a row of logits with 32 bits "
-            "(V < 2**31)".format(logits.size(-1))
+            "(V < 2**30)".format(logits.size(-1))
         )
     _cabi.require_hip(logits, weight)
     device, bitmask, class_tokens, scal, (R, H, N) = _oc_mask(

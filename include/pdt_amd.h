@@ -808,6 +808,40 @@ int pdt_attn_pool_backward(const int64_t *desc, int dtype, const void *score, co
                            void *grad_value, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * The additive ("concat") attention score (reference _attn.py:344-361) with the two halves of W
+ * applied by the caller: e[r, t] = sum_h v[h] * tanh(a[r, h] + b[group(r), t, h]), formed without
+ * a hidden-sized intermediate, and its adjoint with tanh recomputed:
+ *   g = grad_e[r, t] * v[h] * (1 - tanh^2); grad_a[r, h] = sum_t g; grad_b[group, t, h] = sum over
+ *   the group's rows of g; grad_v[h] = sum_{r, t} grad_e[r, t] * tanh.
+ * dtype 0 float32, 1 float64 (accumulated in the same type).  tanh is exactly +-1 with an exact zero
+ * derivative once it saturates (+-inf included); NaN propagates.  No mask: every frame is scored.
+ * desc: PDT_ATTN_DESC_LEN int64 in the layout above, read on the host: [0] nd, [1] R = G * M,
+ *   [2] G, [3] M rows per group (the innermost row dims, over which b and grad_b are broadcast),
+ *   [4] T, [5] H, [6] the element stride of v, [7 ..) the row sizes, then the slots: 0 a (row
+ *   strides, H stride), 1 b (row, T and H strides), 3 grad_e (row and T strides), 4 e (row and T
+ *   strides), 5 grad_a (row and H strides), 6 grad_b (row, T and H strides); slots 2 and 7 are not
+ *   read.  Strides in elements, 0 broadcasts, offsets are 64-bit.  grad_v is H contiguous elements.
+ * pdt_concat_score_workspace_bytes(desc, dtype, kind): kind 0 forward (0 bytes), 1 backward (the
+ *   grad_v partials of every workgroup and, with several frame chunks, those of grad_a; a combine
+ *   pass adds them in a fixed order: no float atomics, bitwise reproducible); -1 for a bad descriptor.
+ * pdt_concat_score_plan (host only, no device work): plan5 = rows per forward tile, H chunks,
+ *   frames per forward workgroup, backward frame chunks (1: grad_a written directly, more: combined),
+ *   backward workspace bytes.  All 0 when R, T or H is 0.
+ * R == 0, T == 0 and H == 0 return PDT_OK without a launch (the sum over no features is 0: the
+ * caller fills e and the gradients with zeros).
+ * ------------------------------------------------------------------------------------- */
+int64_t pdt_concat_score_workspace_bytes(const int64_t *desc, int dtype, int kind);
+
+int pdt_concat_score_plan(const int64_t *desc, int dtype, int64_t *plan5);
+
+int pdt_concat_score(const int64_t *desc, int dtype, const void *a, const void *b, const void *v, void *e,
+                     void *stream);
+
+int pdt_concat_score_backward(const int64_t *desc, int dtype, const void *a, const void *b, const void *v,
+                              const void *grad_e, void *grad_a, void *grad_b, void *grad_v, void *workspace,
+                              int64_t workspace_bytes, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Slicing and chunking (reference _pad.py:257-548, _feats.py:417-930) on two primitives: stable
  * compaction within a row (one workgroup per row; ranks by wave ballot + popcount with a carry)
  * and a copy with an index map and a padding rule.  All lengths, slices and counts are int64;

@@ -140,6 +140,8 @@ extern "C" {
 //     one-launch CTC search for beams of up to 128 prefixes, csrc/ctc_search_wide.hip)
 //     then: pdt_ctc_lm_table_search_plan, pdt_ctc_lookup_lm_search_lds_bytes (host arithmetic only);
 //     pdt_ctc_lm_table_search_workspace_bytes returns 0 for sizes the search does not take
+//     then: pdt_concat_score, pdt_concat_score_backward, pdt_concat_score_workspace_bytes,
+//     pdt_concat_score_plan (csrc/concat_score.hip; no existing entry point changed)
 int pdt_amd_abi_version(void) { return 14; }
 
 int pdt_amd_set_switch(const char *name, int value) {

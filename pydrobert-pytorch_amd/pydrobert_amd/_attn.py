@@ -6,8 +6,10 @@ HIP pass (``csrc/attn.hip``) that reads every key and value row once per group o
 reference materialises two products at the full broadcast shape.  Dot-product and generalized dot-product
 attention make one operator call, ``pydrobert_amd::dot_attention``: the generalized form transforms the query
 (``query @ weight``) instead of every key, and drops ``query . bias``, which is constant along ``dim`` and
-cancels in the softmax.  Any other score (``ConcatSoftAttention``, a subclass with its own ``score``) is
-computed with torch, then ``pydrobert_amd::attention_pool`` does the masked softmax and the weighted sum.
+cancels in the softmax.  ``ConcatSoftAttention`` applies the two halves of its ``W`` in torch and sums
+``v . tanh`` in ``pydrobert_amd::concat_score`` (``csrc/concat_score.hip``), which builds no hidden-sized
+tensor; a subclass with its own ``score`` computes it with torch.  Either score then goes to
+``pydrobert_amd::attention_pool`` for the masked softmax and the weighted sum.
 CPU tensors and other dtypes run the reference's formulas in torch.
 
 Deviation: a masked frame contributes exactly 0 on the HIP path, where the reference multiplies it by 0 (a
@@ -461,6 +463,195 @@ def attention_pool(score: torch.Tensor, value: torch.Tensor, mask: Optional[torc
 
 
 # ----------------------------------------------------------------------------------------------------------
+# the fused ConcatSoftAttention score (csrc/concat_score.hip)
+
+_CA, _CB, _CGE, _CE, _CGA, _CGB = 0, 1, 3, 4, 5, 6  # the descriptor slots the concat kernels read
+
+
+def _concat_geometry(wq: torch.Tensor, wk: torch.Tensor, v: torch.Tensor, dim: int) -> List[int]:
+    n = wk.dim() - 1
+    if wq.dim() != wk.dim() or n < 1 or dim < 0 or dim > n - 1 or wq.shape[dim] != 1:
+        raise RuntimeError(
+            "concat_score takes wq and wk of the same number of dims, a dim in [0, {}] and wq of size 1 "
+            "along it".format(n - 1)
+        )
+    if v.dim() != 1 or wq.shape[-1] != v.shape[0] or wk.shape[-1] != v.shape[0]:
+        raise RuntimeError("concat_score: the last dimension of wq and wk must be v's size")
+    return _bshape(list(wq.shape[:-1]), list(wk.shape[:-1]))
+
+
+class _ConcatPlan:
+    """The rows x T x H reduction of a concat_score call (the row / group rule of _Plan: the row dims where
+    ``wk`` has size 1 form the group and go innermost), its descriptor, and the contiguous layouts the kernels
+    write: e at S, grad_wq at S with ``dim`` at 1, grad_wk with the group's dims at 1."""
+
+    def __init__(self, wq, wk, v, dim, grad_e=None):
+        S = _concat_geometry(wq, wk, v, dim)
+        n, H = len(S), v.shape[0]
+        self.S, self.T, self.H = S, S[dim], H
+        rows = [i for i in range(n) if i != dim and S[i] != 1]  # (a dim of size 0 is a row dim: R is then 0)
+        if len(rows) > _MAX_DIMS:
+            raise RuntimeError("concat_score over more than {} broadcast row dims".format(_MAX_DIMS))
+        group = [i for i in rows if wk.shape[i] == 1]
+        order = [i for i in rows if i not in group] + group
+        self.R = _prod([S[i] for i in rows])
+        self.M = _prod([S[i] for i in group])
+        self.ga_shape = [1 if i == dim else S[i] for i in range(n)] + [H]
+        self.gb_shape = [1 if i in group else S[i] for i in range(n)] + [H]
+        desc = [0] * _DESC_LEN
+        desc[0:7] = [len(order), self.R, self.R // max(self.M, 1), self.M, self.T, H, v.stride(0)]
+        for j, i in enumerate(order):
+            desc[7 + j] = S[i]
+        a_st, b_st = list(wq.expand(S + [H]).stride()), list(wk.expand(S + [H]).stride())
+        strides = {
+            _CA: a_st, _CB: b_st, _CE: _contig_strides(S) + [0], _CGA: _contig_strides(self.ga_shape),
+            _CGB: [0 if i in group else st for i, st in enumerate(_contig_strides(self.gb_shape))],
+        }  # fmt: skip
+        if grad_e is not None:
+            strides[_CGE] = list(grad_e.stride()) + [0]
+        for slot, st in strides.items():
+            base = 7 + _MAX_DIMS + slot * (_MAX_DIMS + 2)
+            for j, i in enumerate(order):
+                desc[base + j] = st[i]
+            desc[base + _MAX_DIMS] = st[dim]
+            desc[base + _MAX_DIMS + 1] = st[n]
+        self.desc = torch.tensor(desc, dtype=torch.int64)
+
+
+def _concat_backward_torch(grad_e: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, v: torch.Tensor):
+    """The three gradients of v . tanh(wq + wk) in differentiable torch operations."""
+    th = torch.tanh(wq + wk)
+    ge = grad_e.unsqueeze(-1)
+    g = ge * v * (1 - th * th)
+    return g.sum_to_size(wq.shape), g.sum_to_size(wk.shape), (ge * th).reshape(-1, v.shape[0]).sum(0)
+
+
+@custom_op("pydrobert_amd::concat_score", mutates_args=())
+def _concat_score_op(wq: torch.Tensor, wk: torch.Tensor, v: torch.Tensor, dim: int) -> torch.Tensor:
+    """e = sum_h v[h] tanh(wq + wk)[..., h] at the broadcast of ``wq`` (size 1 along ``dim``) and ``wk``, without
+    the hidden-sized intermediate."""
+    device = _cabi.require_hip(wq, wk, v)
+    dt = _dtype_code(wq, wk, v)
+    plan = _ConcatPlan(wq, wk, v, dim)
+    if plan.H == 0:  # (the sum over no hidden units)
+        return torch.zeros(plan.S, device=device, dtype=wq.dtype)
+    e = torch.empty(plan.S, device=device, dtype=wq.dtype)
+    if plan.R == 0 or plan.T == 0:  # (an empty score: a batch dim or the attended axis of size 0)
+        return e
+    with _cabi.on_device(device):
+        rc = _cabi.lib().pdt_concat_score(
+            plan.desc.data_ptr(), dt, wq.data_ptr(), wk.data_ptr(), v.data_ptr(), e.data_ptr(),
+            _cabi.stream_ptr(device),
+        )  # fmt: skip
+    _cabi.check(rc, "pdt_concat_score")
+    return e
+
+
+@_concat_score_op.register_fake
+def _(wq, wk, v, dim):
+    return wq.new_empty(_concat_geometry(wq, wk, v, dim))
+
+
+@custom_op("pydrobert_amd::concat_score_backward", mutates_args=())
+def _concat_score_backward_op(
+    grad_e: torch.Tensor, wq: torch.Tensor, wk: torch.Tensor, v: torch.Tensor, dim: int
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(grad_wq, grad_wk, grad_v) in the inputs' shapes, tanh recomputed.  The kernels sum grad_wk over the
+    group; what other broadcast ``wq`` had is summed here."""
+    device = _cabi.require_hip(grad_e, wq, wk, v)
+    dt = _dtype_code(wq, wk, v)
+    g = grad_e.detach().to(wq.dtype)
+    plan = _ConcatPlan(wq, wk, v, dim, g.expand(_concat_geometry(wq, wk, v, dim)))
+    if plan.R == 0 or plan.T == 0 or plan.H == 0:
+        return torch.zeros_like(wq), torch.zeros_like(wk), torch.zeros_like(v)
+    nbytes = _cabi.lib().pdt_concat_score_workspace_bytes(plan.desc.data_ptr(), dt, 1)
+    if nbytes < 0:
+        raise RuntimeError("pdt_concat_score_workspace_bytes: invalid descriptor")
+    ws = torch.empty((max(1, nbytes),), device=device, dtype=torch.uint8)
+    ga = torch.empty(plan.ga_shape, device=device, dtype=wq.dtype)
+    gb = torch.empty(plan.gb_shape, device=device, dtype=wq.dtype)
+    gv = torch.empty((plan.H,), device=device, dtype=wq.dtype)
+    with _cabi.on_device(device):
+        rc = _cabi.lib().pdt_concat_score_backward(
+            plan.desc.data_ptr(), dt, wq.data_ptr(), wk.data_ptr(), v.data_ptr(), g.data_ptr(), ga.data_ptr(),
+            gb.data_ptr(), gv.data_ptr(), ws.data_ptr(), ws.numel(), _cabi.stream_ptr(device),
+        )  # fmt: skip
+    _cabi.check(rc, "pdt_concat_score_backward")
+    return ga.sum_to_size(wq.shape), gb.sum_to_size(wk.shape), gv
+
+
+@_concat_score_backward_op.register_fake
+def _(grad_e, wq, wk, v, dim):
+    return torch.empty_like(wq), torch.empty_like(wk), torch.empty_like(v)
+
+
+def _concat_setup_context(ctx, inputs, output):
+    wq, wk, v, dim = inputs
+    ctx.save_for_backward(wq, wk, v)
+    ctx.dim = dim
+
+
+def _concat_backward(ctx, grad_e):
+    wq, wk, v = ctx.saved_tensors
+    ga, gb, gv = torch.ops.pydrobert_amd.concat_score_backward(grad_e, wq, wk, v, ctx.dim)
+    need = ctx.needs_input_grad
+    return ga if need[0] else None, gb if need[1] else None, gv if need[2] else None, None
+
+
+def _concat_backward_setup_context(ctx, inputs, output):
+    ctx.save_for_backward(*inputs[:4])
+
+
+def _concat_backward_backward(ctx, gg_wq, gg_wk, gg_v):
+    """The derivative of the backward operator: the torch body's, in differentiable torch operations."""
+    saved = ctx.saved_tensors
+    with torch.enable_grad():
+        leaves = [t.detach().requires_grad_() for t in saved]
+        outs = _concat_backward_torch(*leaves)
+        live = [(o, gg) for o, gg in zip(outs, (gg_wq, gg_wk, gg_v)) if gg is not None and o.requires_grad]
+        targets = [t for i, t in enumerate(leaves) if ctx.needs_input_grad[i]]
+        second = iter(
+            torch.autograd.grad([o for o, _ in live], targets, [gg for _, gg in live], allow_unused=True)
+            if live and targets else [None] * len(targets)
+        )  # fmt: skip
+    return tuple(next(second) if ctx.needs_input_grad[i] else None for i in range(4)) + (None,)
+
+
+register_autograd("pydrobert_amd::concat_score", _concat_backward, setup_context=_concat_setup_context)
+register_autograd(
+    "pydrobert_amd::concat_score_backward", _concat_backward_backward, setup_context=_concat_backward_setup_context
+)
+
+
+def concat_score(wq: torch.Tensor, wk: torch.Tensor, v: torch.Tensor, dim: int) -> torch.Tensor:
+    """The fused additive score of ROCm tensors (``pydrobert_amd::concat_score``)."""
+    if not torch.jit.is_scripting():
+        if not torch.jit.is_tracing() and _cabi.plain_call(wq, wk, v):
+            return _concat_score_op._init_fn(wq, wk, v, dim)
+    return torch.ops.pydrobert_amd.concat_score(wq, wk, v, dim)
+
+
+def _concat_hip_route(wq: torch.Tensor, wk: torch.Tensor, v: torch.Tensor, dim: int) -> bool:
+    """True when the kernels compute what the torch body does: float32 / float64 tensors of one dtype on one ROCm
+    device, a non-negative ``dim`` along which ``wq`` has size 1, and at most eight row dims."""
+    dt = wq.dtype
+    if dt != torch.float32 and dt != torch.float64:
+        return False
+    if not wq.is_cuda or wk.device != wq.device or v.device != wq.device or wk.dtype != dt or v.dtype != dt:
+        return False
+    n = wk.dim() - 1
+    if wq.dim() != wk.dim() or dim < 0 or dim > n - 1 or wq.size(dim) != 1:
+        return False
+    if v.dim() != 1 or wq.size(-1) != v.size(0) or wk.size(-1) != v.size(0):
+        return False
+    rows = 0
+    for i in range(n):
+        if i != dim and (wq.size(i) != 1 or wk.size(i) != 1):
+            rows += 1
+    return rows <= 8  # (PDT_ATTN_MAX_DIMS)
+
+
+# ----------------------------------------------------------------------------------------------------------
 # modules
 
 class GlobalSoftAttention(torch.nn.Module, metaclass=abc.ABCMeta):
@@ -637,16 +828,24 @@ class GeneralizedDotProductSoftAttention(GlobalSoftAttention):
     reset_parameters = torch.jit.unused(torch.nn.Linear.reset_parameters)
 
 
+def _concat_score_torch(wq: torch.Tensor, wk: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
+    """v . tanh(wq + wk) in torch, at the full broadcast shape times the hidden size: CPU tensors, other dtypes."""
+    return torch.nn.functional.linear(torch.tanh(wq + wk), v.unsqueeze(0), None).squeeze(-1)
+
+
 def _concat_score(
     query: torch.Tensor, key: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], v: torch.Tensor,
     dim: int,
 ) -> torch.Tensor:  # fmt: skip
     """v . tanh(W [query, key] + b) with the query and key halves of W applied before broadcasting, so no
-    expanded concatenation is built (the reference's _attn.py:344-361 expands both)."""
+    expanded concatenation is built (the reference's _attn.py:344-361 expands both); on ROCm tensors the sum
+    over the hidden units runs in ``pydrobert_amd::concat_score`` and no hidden-sized tensor is built either."""
     Dq = query.size(-1)
     wq = torch.nn.functional.linear(query.unsqueeze(dim), weight[:, :Dq], bias)
     wk = torch.nn.functional.linear(key, weight[:, Dq:], None)
-    return torch.nn.functional.linear(torch.tanh(wq + wk), v.unsqueeze(0), None).squeeze(-1)
+    if _concat_hip_route(wq, wk, v, dim):
+        return concat_score(wq, wk, v, dim)
+    return _concat_score_torch(wq, wk, v)
 
 
 class ConcatSoftAttention(GlobalSoftAttention):

@@ -26,7 +26,9 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # host-only plans of the searches with an n-gram model (pdt_ctc_lm_table_search_plan,
 # pdt_ctc_lookup_lm_search_lds_bytes) and the backward of relaxed sampling (pdt_relaxed_backward_parts,
 # pdt_relaxed_backward_workspace_bytes, pdt_relaxed_gumbel_backward, pdt_relaxed_bernoulli_backward) and the
-# host-only plans of BeamSearch's kernels (pdt_beam_search_step_plan, pdt_beam_search_table_plan).
+# host-only plans of BeamSearch's kernels (pdt_beam_search_step_plan, pdt_beam_search_table_plan) and the fused
+# ConcatSoftAttention score (pdt_concat_score, pdt_concat_score_backward, pdt_concat_score_workspace_bytes,
+# pdt_concat_score_plan).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -214,6 +216,10 @@ SIGNATURES = {
     ),
     "pdt_attn_pool": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_attn_pool_backward": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_concat_score_workspace_bytes": (_I64, [_P, _INT, _INT]),
+    "pdt_concat_score_plan": (_INT, [_P, _INT, _P]),
+    "pdt_concat_score": (_INT, [_P, _INT, _P, _P, _P, _P, _P]),
+    "pdt_concat_score_backward": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_compact_mask": (_INT, [_P, _I64, _I64, _I64, _I64, _P, _P, _I64, _I64, _P, _P]),
     "pdt_gather_steps": (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _I64, _INT, _P, _P, _P]),
     "pdt_chunk_by_slices": (_INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _INT, _P, _I64, _P, _P]),

@@ -657,6 +657,54 @@ int pdt_sparse_image_warp_backward(const float *grad_out, const float *train_poi
                                    int values_are_grid, int mode, int padding, float *grad_image,
                                    void *workspace, void *stream);
 
+/* Gradients of the warps with respect to WHERE they sample (what autograd derives through grid_sample's
+ * grid in the reference, _img.py:436): per pixel, grad_out times the derivative of the bilinear blend,
+ * chained through the padding rule (torch's clip_coordinates_set_grad / reflect_coordinates_set_grad), the
+ * un-normalisation and the grid formula.  grad_out and image (N,C,H,W) in one type (float, or double for the
+ * _f64 entries); the outputs are float32 (N,H,W,2), overwritten.  mode = 1 (nearest): zeros.  Limits and
+ * argument checks are those of the forward entry points.
+ * pdt_dense_image_warp_flow_backward: grad_flow, in the flow's own order (flow_is_hw).
+ * pdt_sparse_image_warp_position_backward: grad_values = the gradient with respect to the spline's value
+ *   at every pixel in (x, y) order -- the G of pdt_spline_eval_adjoint over the pixel lattice.  solution: the
+ *   (N, M + 3, 2) float64 solution of the spline (pdt_spline_solve of the forward call's train_points /
+ *   train_values); grad_flow: optional (N,H,W,2) gradient of the returned flow (flow form only), (h, w)-
+ *   ordered when grad_flow_is_hw, added.  workspace: pdt_spline_workspace_bytes(N, M, 2, 2) bytes.
+ *
+ * pdt_spline_eval_adjoint: the query-sized half of the spline's backward as a deterministic two-stage
+ *   reduction over the Q queries (float64 sums; per-workgroup partials, then a fixed-order sum; the same
+ *   bits every run).  grad_out G (N,Q,O) float; train_points (N,T,I); solution (N, T+I+1, O) float64;
+ *   query_points (N,Q,I), or NULL = the pixel lattice x_q = (q % W, q / W) of an H x W image (I = 2,
+ *   Q = H * W).  Out, float64: rhs (N, T+I+1, O) = [Phi(x, c)^T G; [x 1]^T G], the right-hand side of the
+ *   adjoint system; grad_points (N,T,I) = -sum_q (G w^T)[q,t] slope(r_qt) (x_q - c_t), the evaluation's
+ *   share of the centres' gradient; grad_query (N,Q,I) or NULL = the queries' gradient.  I, O <= 4, else
+ *   PDT_E_UNSUPPORTED.  workspace: plan[2] bytes of pdt_spline_eval_adjoint_plan.
+ * pdt_spline_eval_adjoint_plan (host only): returns the form -- 0: a workgroup holds all T + I + 1 rows and
+ *   several slices of q; 1: more rows than a workgroup has lanes, row tiles -- or an error code, and fills
+ *   plan[6] (may be NULL): form, workgroups per batch element, workspace bytes, grad_query's kernel reads
+ *   solution and centres from LDS (1) or global memory (0), slices, queries per workgroup. */
+int pdt_dense_image_warp_flow_backward(const float *grad_out, const float *image, const float *flow, int64_t N,
+                                       int64_t C, int64_t H, int64_t W, int flow_is_hw, int mode, int padding,
+                                       float *grad_flow, void *stream);
+int pdt_dense_image_warp_flow_backward_f64(const double *grad_out, const double *image, const float *flow,
+                                           int64_t N, int64_t C, int64_t H, int64_t W, int flow_is_hw, int mode,
+                                           int padding, float *grad_flow, void *stream);
+int pdt_sparse_image_warp_position_backward(const float *grad_out, const float *image, const float *train_points,
+                                            const double *solution, int64_t N, int64_t C, int64_t H, int64_t W,
+                                            int64_t M, int order, int values_are_grid, int mode, int padding,
+                                            const float *grad_flow, int grad_flow_is_hw, float *grad_values,
+                                            void *workspace, void *stream);
+int pdt_sparse_image_warp_position_backward_f64(const double *grad_out, const double *image,
+                                                const float *train_points, const double *solution, int64_t N,
+                                                int64_t C, int64_t H, int64_t W, int64_t M, int order,
+                                                int values_are_grid, int mode, int padding, const float *grad_flow,
+                                                int grad_flow_is_hw, float *grad_values, void *workspace,
+                                                void *stream);
+int pdt_spline_eval_adjoint_plan(int64_t N, int64_t T, int64_t I, int64_t O, int64_t Q, int64_t *plan);
+int pdt_spline_eval_adjoint(const float *grad_out, const float *train_points, const double *solution,
+                            const float *query_points, int64_t N, int64_t T, int64_t I, int64_t O, int64_t Q,
+                            int64_t H, int64_t W, int order, double *rhs, double *grad_points,
+                            double *grad_query, void *workspace, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * Back-off n-gram language model scoring (reference _lm.py:403-515, LookupLanguageModel
  * :518-1110), the on-device LM of CTCPrefixSearch / BeamSearch with shallow fusion.

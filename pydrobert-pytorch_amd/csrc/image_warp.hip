@@ -31,6 +31,8 @@ struct WarpArgsT {
   float *flow_out;     // sparse, optional (N,H,W,2)
   int flow_out_flip;
   PT *grad_image;      // BACKWARD: (N,C,H,W), zeroed by the caller; `out` then holds grad_out
+  float *grad_pos;     // WARP_POSITION: (N,H,W,2), dL/d(flow) or dL/d(spline value); `out` holds grad_out
+  const float *grad_flow_in;  // WARP_POSITION, sparse, optional: (N,H,W,2) added (flow_out_flip: its order)
 };
 using WarpArgs = WarpArgsT<float>;
 
@@ -40,10 +42,22 @@ using WarpArgs = WarpArgsT<float>;
 // the image's type (_img.py:420, :537-538) but forms the sampling grid and samples it in the
 // image's type (:423-436), so here the flow / spline value stays float and everything from the grid
 // on (un-normalisation, padding, weights, blend, the adjoint's atomics) is double.
+//
+// WARP_POSITION = gradient with respect to WHERE a pixel samples: per pixel dL/d(ix, iy) = sum over the
+// channels of grad_out x the derivative of the bilinear blend (the four taps under the forward's validity
+// tests), chained through the padding rule (img_sample.hpp: clip_coord_factor / reflect_coord_factor,
+// torch's *_set_grad), the un-normalisation (size / 2) and the grid formula (-2 / size for a flow: -1
+// together; the no-flow spline form keeps size / 2).  Each pixel writes its own two numbers: no atomics.
+// Dense: the flow's gradient in the flow's own order (flip).  Sparse: the gradient with respect to the
+// spline's value at the pixel in (x, y) order -- what pdt_spline_eval_adjoint reduces -- plus the caller's
+// gradient of the returned flow (grad_flow_in, in flow_out_flip's order).
 constexpr int kPixPerWG = 2048;
-template <bool BACKWARD, typename PT = float>
+enum { WARP_FORWARD = 0, WARP_ADJOINT = 1, WARP_POSITION = 2 };
+template <int FORM, typename PT = float>
 __global__ void __launch_bounds__(256) image_warp_kernel(const WarpArgsT<PT> a) {
   using CT = PT;  // coordinate type
+  constexpr bool BACKWARD = FORM == WARP_ADJOINT;
+  constexpr bool POSITION = FORM == WARP_POSITION;
   extern __shared__ __align__(16) unsigned char smem[];
   float *lk = reinterpret_cast<float *>(smem);  // knots (M,2) then weights (M+3,2)
   float *lw = lk + 2 * a.M;
@@ -93,7 +107,7 @@ __global__ void __launch_bounds__(256) image_warp_kernel(const WarpArgsT<PT> a) 
         gx = sx;
         gy = sy;
       } else {
-        if (!BACKWARD && a.flow_out) {
+        if (FORM == WARP_FORWARD && a.flow_out) {
           float *fo = a.flow_out + ((n * H + h) * (int64_t)W + w) * 2;
           fo[0] = a.flow_out_flip ? sy : sx;
           fo[1] = a.flow_out_flip ? sx : sy;
@@ -112,6 +126,46 @@ __global__ void __launch_bounds__(256) image_warp_kernel(const WarpArgsT<PT> a) 
     const PT *img = a.image + n * a.C * plane;
     PT *o = a.out + n * a.C * plane + pix;
     PT *gi = a.grad_image + n * a.C * plane;
+    if (POSITION) {
+      // (sx, sy): dL/d(the x and y component of the flow or of the spline's value) at this pixel
+      CT sx = CT(0), sy = CT(0);
+      if (a.mode == INTERP_BILINEAR) {  // (nearest: piecewise constant in the position)
+        const CT x0f = floor(ix), y0f = floor(iy);
+        const int x0 = (int)x0f, y0 = (int)y0f, x1 = x0 + 1, y1 = y0 + 1;
+        const CT wx1 = ix - x0f, wy1 = iy - y0f, wx0 = (x0f + CT(1)) - ix, wy0 = (y0f + CT(1)) - iy;
+        const bool vx0 = x0 >= 0 && x0 < W, vx1 = x1 >= 0 && x1 < W;
+        const bool vy0 = y0 >= 0 && y0 < H, vy1 = y1 >= 0 && y1 < H;
+        CT dix = CT(0), diy = CT(0);
+        for (int c = 0; c < a.C; ++c) {
+          const PT *pl = img + c * plane;
+          const PT g = o[c * plane];
+          if (vx0 && vy0) { const PT t = pl[(int64_t)y0 * W + x0] * g; dix -= t * wy0; diy -= t * wx0; }
+          if (vx1 && vy0) { const PT t = pl[(int64_t)y0 * W + x1] * g; dix += t * wy0; diy -= t * wx1; }
+          if (vx0 && vy1) { const PT t = pl[(int64_t)y1 * W + x0] * g; dix -= t * wy1; diy += t * wx0; }
+          if (vx1 && vy1) { const PT t = pl[(int64_t)y1 * W + x1] * g; dix += t * wy1; diy += t * wx1; }
+        }
+        // padding rule, then un-normalisation x grid formula: size / 2 x -2 / size = -1 for a flow
+        const CT fx = source_index_factor<CT>(gx, W, a.padding), fy = source_index_factor<CT>(gy, H, a.padding);
+        const bool grid = a.knots && a.as_grid;
+        sx = dix * fx * (grid ? CT(0.5) * (CT)W : CT(-1));
+        sy = diy * fy * (grid ? CT(0.5) * (CT)H : CT(-1));
+      }
+      const int64_t at = ((n * H + h) * (int64_t)W + w) * 2;
+      float r0 = (float)sx, r1 = (float)sy;
+      if (a.knots) {
+        if (a.grad_flow_in) {
+          r0 += a.grad_flow_in[at + (a.flow_out_flip ? 1 : 0)];
+          r1 += a.grad_flow_in[at + (a.flow_out_flip ? 0 : 1)];
+        }
+      } else if (a.flip) {
+        const float t = r0;
+        r0 = r1;
+        r1 = t;
+      }
+      a.grad_pos[at] = r0;
+      a.grad_pos[at + 1] = r1;
+      continue;
+    }
     if (a.mode == INTERP_NEAREST) {
       const int xn = (int)nearbyint(ix), yn = (int)nearbyint(iy);
       const bool ok = xn >= 0 && xn < W && yn >= 0 && yn < H;
@@ -353,7 +407,7 @@ static pdt::WarpArgsT<PT> warp_args(const PT *image, PT *out, int64_t N, int64_t
 }
 
 // image_warp_kernel over kPixPerWG pixels per workgroup: the adjoint (grad_image set: zeroed here, the
-// kernel scatters into it) or the forward gather
+// kernel scatters into it), the position gradient (grad_pos set) or the forward gather
 template <typename PT>
 static int launch_image_warp(const pdt::WarpArgsT<PT> &a, size_t smem, hipStream_t stream) {
   using namespace pdt;
@@ -362,9 +416,11 @@ static int launch_image_warp(const pdt::WarpArgsT<PT> &a, size_t smem, hipStream
   if (a.grad_image) {
     hipError_t e = hipMemsetAsync(a.grad_image, 0, (size_t)a.N * a.C * plane * sizeof(PT), stream);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((image_warp_kernel<true, PT>), grid, dim3(256), smem, stream, a);
+    hipLaunchKernelGGL((image_warp_kernel<WARP_ADJOINT, PT>), grid, dim3(256), smem, stream, a);
+  } else if (a.grad_pos) {
+    hipLaunchKernelGGL((image_warp_kernel<WARP_POSITION, PT>), grid, dim3(256), smem, stream, a);
   } else {
-    hipLaunchKernelGGL((image_warp_kernel<false, PT>), grid, dim3(256), smem, stream, a);
+    hipLaunchKernelGGL((image_warp_kernel<WARP_FORWARD, PT>), grid, dim3(256), smem, stream, a);
   }
   return (int)hipGetLastError();
 }
@@ -519,6 +575,89 @@ int pdt_sparse_image_warp_backward_f64(const double *grad_out, const float *trai
   return sparse_warp_launch<double>(nullptr, train_points, train_values, N, C, H, W, M, order,
                                     regularization_weight, values_are_grid, mode, padding,
                                     const_cast<double *>(grad_out), nullptr, 0, grad_image, workspace, stream);
+}
+
+// The position gradients (image_warp_kernel<WARP_POSITION>): the forward entry points' limits and checks.
+extern "C++" {
+template <typename PT>
+static int dense_flow_backward_launch(const PT *grad_out, const PT *image, const float *flow, int64_t N, int64_t C,
+                                      int64_t H, int64_t W, int flow_is_hw, int mode, int padding, float *grad_flow,
+                                      void *stream) {
+  using namespace pdt;
+  if (N < 0 || C < 0 || H < 0 || W < 0 || mode < 0 || mode > 1 || padding < 0 || padding > 2)
+    return PDT_E_ARG;
+  if (N == 0 || H == 0 || W == 0) return PDT_OK;
+  if (!grad_flow) return PDT_E_ARG;
+  if (C == 0 || mode == INTERP_NEAREST)  // (no launch: a nearest sample does not move with its position)
+    return (int)hipMemsetAsync(grad_flow, 0, (size_t)N * H * W * 2 * sizeof(float), (hipStream_t)stream);
+  if (!grad_out || !image || !flow) return PDT_E_ARG;
+  if (H * W >= (1ll << 31) || N > 65535) return PDT_E_TOO_LONG;
+  WarpArgsT<PT> a = warp_args(image, const_cast<PT *>(grad_out), N, C, H, W, mode, padding, (PT *)nullptr);
+  a.flow = flow; a.flip = flow_is_hw; a.grad_pos = grad_flow;
+  return launch_image_warp(a, 0, (hipStream_t)stream);
+}
+
+// solution: the (N, M + 3, 2) float64 solution of the spline (pdt_spline_solve); its float copy goes to the
+// head of the workspace, as in sparse_warp_launch
+template <typename PT>
+static int sparse_position_backward_launch(const PT *grad_out, const PT *image, const float *train_points,
+                                           const double *solution, int64_t N, int64_t C, int64_t H, int64_t W,
+                                           int64_t M, int order, int values_are_grid, int mode, int padding,
+                                           const float *grad_flow, int grad_flow_is_hw, float *grad_values,
+                                           void *workspace, void *stream) {
+  using namespace pdt;
+  if (N < 0 || C < 0 || H < 0 || W < 0 || M < 1 || order < 1 || mode < 0 || mode > 1 ||
+      padding < 0 || padding > 2)
+    return PDT_E_ARG;
+  if (N == 0 || H == 0 || W == 0) return PDT_OK;
+  if (!grad_values || (C > 0 && (!grad_out || !image)) || !train_points || !solution || !workspace)
+    return PDT_E_ARG;
+  if (grad_flow && values_are_grid) return PDT_E_ARG;  // (the no-flow form returns no flow)
+  if (H * W >= (1ll << 31) || N > 65535) return PDT_E_TOO_LONG;
+  const int64_t total = N * (M + 3) * 2;
+  float *wvf = reinterpret_cast<float *>(workspace);
+  hipLaunchKernelGGL(cast_wv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     solution, wvf, total);
+  WarpArgsT<PT> a = warp_args(image, const_cast<PT *>(grad_out), N, C, H, W, mode, padding, (PT *)nullptr);
+  a.knots = train_points; a.wv = wvf; a.M = (int)M; a.order = order; a.as_grid = values_are_grid;
+  a.grad_pos = grad_values; a.grad_flow_in = grad_flow; a.flow_out_flip = grad_flow_is_hw;
+  return launch_image_warp(a, (size_t)(2 * M + 2 * (M + 3)) * sizeof(float), (hipStream_t)stream);
+}
+}  // extern "C++"
+
+int pdt_dense_image_warp_flow_backward(const float *grad_out, const float *image, const float *flow, int64_t N,
+                                       int64_t C, int64_t H, int64_t W, int flow_is_hw, int mode, int padding,
+                                       float *grad_flow, void *stream) {
+  return dense_flow_backward_launch<float>(grad_out, image, flow, N, C, H, W, flow_is_hw, mode, padding, grad_flow,
+                                           stream);
+}
+
+int pdt_dense_image_warp_flow_backward_f64(const double *grad_out, const double *image, const float *flow,
+                                           int64_t N, int64_t C, int64_t H, int64_t W, int flow_is_hw, int mode,
+                                           int padding, float *grad_flow, void *stream) {
+  return dense_flow_backward_launch<double>(grad_out, image, flow, N, C, H, W, flow_is_hw, mode, padding,
+                                            grad_flow, stream);
+}
+
+int pdt_sparse_image_warp_position_backward(const float *grad_out, const float *image, const float *train_points,
+                                            const double *solution, int64_t N, int64_t C, int64_t H, int64_t W,
+                                            int64_t M, int order, int values_are_grid, int mode, int padding,
+                                            const float *grad_flow, int grad_flow_is_hw, float *grad_values,
+                                            void *workspace, void *stream) {
+  return sparse_position_backward_launch<float>(grad_out, image, train_points, solution, N, C, H, W, M, order,
+                                                values_are_grid, mode, padding, grad_flow, grad_flow_is_hw,
+                                                grad_values, workspace, stream);
+}
+
+int pdt_sparse_image_warp_position_backward_f64(const double *grad_out, const double *image,
+                                                const float *train_points, const double *solution, int64_t N,
+                                                int64_t C, int64_t H, int64_t W, int64_t M, int order,
+                                                int values_are_grid, int mode, int padding, const float *grad_flow,
+                                                int grad_flow_is_hw, float *grad_values, void *workspace,
+                                                void *stream) {
+  return sparse_position_backward_launch<double>(grad_out, image, train_points, solution, N, C, H, W, M, order,
+                                                 values_are_grid, mode, padding, grad_flow, grad_flow_is_hw,
+                                                 grad_values, workspace, stream);
 }
 
 }  // extern "C"

@@ -99,6 +99,33 @@ __device__ __forceinline__ CT source_index(CT g, int size, int padding) {
   return x;
 }
 
+// The derivatives of clip_coord / reflect_coord with respect to their argument, as torch's
+// clip_coordinates_set_grad / reflect_coordinates_set_grad choose them at the kinks: the clip passes
+// nothing at or beyond its limits (x <= 0, x >= size - 1); the reflection's sign is that of x - low,
+// turned once more on an odd number of folds (a zero span passes nothing).
+template <typename CT>
+__device__ __forceinline__ CT clip_coord_factor(CT x, int size) {
+  return (x <= CT(0) || x >= (CT)(size - 1)) ? CT(0) : CT(1);
+}
+template <typename CT>
+__device__ __forceinline__ CT reflect_coord_factor(CT x, int twice_low, int twice_high) {
+  if (twice_low == twice_high) return CT(0);
+  const CT mn = (CT)twice_low * CT(0.5), span = (CT)(twice_high - twice_low) * CT(0.5);
+  x -= mn;
+  const CT sign = x < CT(0) ? CT(-1) : CT(1);
+  const int flips = (int)floor(fabs(x) / span);
+  return (flips & 1) ? -sign : sign;
+}
+// d source_index / d unnormalize(g): the padding rule's factor (zeros padding: 1)
+template <typename CT>
+__device__ __forceinline__ CT source_index_factor(CT g, int size, int padding) {
+  const CT x = unnormalize(g, size);
+  if (padding == PAD_BORDER) return clip_coord_factor(x, size);
+  if (padding == PAD_REFLECTION)
+    return reflect_coord_factor(x, -1, 2 * size - 1) * clip_coord_factor(reflect_coord(x, -1, 2 * size - 1), size);
+  return CT(1);
+}
+
 // warp_1d_grid's spline (_img.py:283-302) in closed form.  Knots c0 < c1 < c2 = {lo, dst, up}, values
 // {lo, src, up}; the bordered 5 x 5 system [[A, [c 1]], [[c 1]^T, 0]] [w; v] = [f; 0] with A_ij =
 // phi(|c_i - c_j|): the two constraints leave w = alpha u, u = (c1 - c2, c2 - c0, c0 - c1); u kills

@@ -3,6 +3,8 @@
 // Replaces, from the reference's _img.py:
 //   polyharmonic_spline (:59-150)            -> spline_solve_kernel + spline_apply_kernel
 //   warp_1d_grid (:268-303)                  -> warp_1d_grid_kernel (3-knot spline, 5x5 solve)
+//   the spline's backward, query-sized half  -> spline_adjoint_partial_kernel + spline_adjoint_sum_kernel
+//       (what autograd derives through :67-76)  (+ spline_adjoint_gx_kernel for the queries' gradient)
 // The small dense systems are solved in float64 (partial pivoting).  pdt::spline_solve also serves
 // the sparse image warp (image_warp.hip, through img_launch.hpp).
 #include "img_launch.hpp"
@@ -175,6 +177,228 @@ static int spline_apply(const float *c, const double *wv, const float *x, int64_
   return (int)hipGetLastError();
 }
 
+// ---- the evaluation's adjoint --------------------------------------------------------------------
+// out = Phi(x, c) w + [x 1] v and G = dL/dout (N, Q, O): the query-sized sums of the spline's backward,
+//   rhs[t]     = sum_q phi(r_qt) G[q]            (t < T; the adjoint system's right-hand side)
+//   rhs[T + k] = sum_q x_qk G[q], rhs[T + I] = sum_q G[q]
+//   g_c[t]     = -sum_q (G[q] . w[t]) slope(r_qt) (x_q - c_t)          (the evaluation's share)
+// as a reduction over q that never forms anything of size Q x T.  phi and slope = phi'(r) / r as the
+// float64 formulas of the host's backward have them (slope 0 at r = 0, the log clamped at eps).
+//
+// Lane = (row, slice of q): a row is a centre t or one of the I + 1 affine rows, and keeps its centre, its
+// weights and its O + I float64 sums in registers for the whole walk; the workgroup's `nsl` slices step
+// through its queries side by side (slice s takes q0 + s, q0 + s + nsl, ...), so no lane waits for a
+// cross-lane sum per centre.  Rows vary fastest within the workgroup: a wave's lanes read a handful of
+// neighbouring queries.  The slices are combined once per workgroup in LDS, in slice order, and the
+// workgroup stores its partial sums; spline_adjoint_sum_kernel adds the workgroups' partials in their
+// fixed order -- no floating-point atomics, the same bits every run.
+// Systems of more than kAdjRows rows: one slice, the rows in tiles of kAdjRows over further workgroups.
+constexpr int kAdjRows = 256;     // threads of a workgroup = rows x slices
+constexpr int kAdjMinSteps = 64;  // queries a slice walks at least (while there are that many)
+constexpr int kAdjMaxChunks = 128;  // workgroups along q per batch element at most (bounds the partials)
+constexpr int kAdjMaxDim = 4;     // I and O served in registers
+
+struct AdjPlan {
+  int form;        // 0: all rows in one workgroup, nsl slices; 1: row tiles, one slice
+  int nsl, tiles, chunks, qper;  // slices, row tiles, workgroups along q, queries per workgroup
+  int gx_staged;   // spline_adjoint_gx_kernel reads solution and centres from LDS (else global memory)
+  int64_t partial_doubles;  // per batch element
+};
+static AdjPlan adj_plan(int64_t T, int64_t I, int64_t O, int64_t Q) {
+  AdjPlan p;
+  const int64_t S = T + I + 1;
+  p.form = S > kAdjRows ? 1 : 0;
+  p.nsl = p.form ? 1 : (int)(kAdjRows / S);
+  p.tiles = (int)((S + kAdjRows - 1) / kAdjRows);
+  const int64_t per_min = (int64_t)p.nsl * kAdjMinSteps;
+  int64_t chunks = (Q + per_min - 1) / per_min;
+  if (chunks > kAdjMaxChunks) chunks = kAdjMaxChunks;
+  if (chunks < 1) chunks = 1;
+  int64_t qper = (Q + chunks - 1) / chunks;
+  qper = (qper + p.nsl - 1) / p.nsl * p.nsl;
+  if (qper < p.nsl) qper = p.nsl;
+  p.chunks = (int)((Q + qper - 1) / qper);
+  if (p.chunks < 1) p.chunks = 1;
+  p.qper = (int)qper;
+  p.gx_staged = spline_apply_lds_bytes(T, I, O) <= kSplineLdsCap;
+  p.partial_doubles = (int64_t)p.chunks * (S * O + T * I);
+  return p;
+}
+
+__device__ __forceinline__ double ipow_d(double r, int k) {
+  double p = 1.0;
+  for (int i = 0; i < k; ++i) p *= r;
+  return p;
+}
+// phi(r) and phi'(r) / r (zero where r = 0: the direction vector vanishes there)
+__device__ __forceinline__ void phi_and_slope_d(double r, int order, double &phi, double &slope) {
+  const double eps = (double)FLT_EPSILON;
+  const bool pos = r > 0.0;
+  const double safe = pos ? r : 1.0;
+  const double pw = order >= 2 ? ipow_d(safe, order - 2) : 1.0 / safe;  // safe^(order - 2)
+  if (order & 1) {
+    phi = ipow_d(r, order);
+    slope = (double)order * pw;
+  } else {
+    const double lg = log(fmax(safe, eps));
+    phi = ipow_d(r, order) * lg;
+    slope = pw * (safe > eps ? (double)order * lg + 1.0 : (double)order * log(eps));
+  }
+  if (!pos) slope = 0.0;
+}
+
+// x: (N, Q, I) or null = the pixel lattice (q % W, q / W) with I = 2.  part: (N, chunks, S*O + T*I).
+__global__ void __launch_bounds__(kAdjRows)
+spline_adjoint_partial_kernel(const float *__restrict__ G, const float *__restrict__ c,
+                              const double *__restrict__ sol, const float *__restrict__ x, int T, int I, int O, int Q,
+                              int W, int order, int nsl, int tiles, int qper, double *__restrict__ part) {
+  __shared__ double buf[kAdjRows * 2 * kAdjMaxDim];
+  const int S = T + I + 1, NV = O + I;
+  const int64_t n = blockIdx.y;
+  const int tile = (int)(blockIdx.x % (unsigned)tiles), chunk = (int)(blockIdx.x / (unsigned)tiles);
+  const int rows = min(kAdjRows, S - tile * kAdjRows);  // rows of this workgroup
+  const int tid = (int)threadIdx.x;
+  const int s = tid / rows, rr = tid - s * rows, row = tile * kAdjRows + rr;
+  const bool live = s < nsl;
+  double acc[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0}, gcv[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0};
+  double ct[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0}, wt[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0};
+  if (live && row < T) {
+#pragma unroll
+    for (int k = 0; k < kAdjMaxDim; ++k)
+      if (k < I) ct[k] = (double)c[(n * T + row) * I + k];
+#pragma unroll
+    for (int o = 0; o < kAdjMaxDim; ++o)
+      if (o < O) wt[o] = sol[(n * S + row) * O + o];
+  }
+  const int q0 = chunk * qper, q1 = min(Q, q0 + qper);
+  if (live) {
+    for (int q = q0 + s; q < q1; q += nsl) {
+      double xq[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0}, g[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0};
+      if (x) {
+#pragma unroll
+        for (int k = 0; k < kAdjMaxDim; ++k)
+          if (k < I) xq[k] = (double)x[(n * Q + q) * I + k];
+      } else {
+        const int h = q / W;
+        xq[0] = (double)(q - h * W);
+        xq[1] = (double)h;
+      }
+#pragma unroll
+      for (int o = 0; o < kAdjMaxDim; ++o)
+        if (o < O) g[o] = (double)G[(n * Q + q) * O + o];
+      if (row < T) {
+        double d[kAdjMaxDim], d2 = 0.0, a = 0.0, phi, slope;
+#pragma unroll
+        for (int k = 0; k < kAdjMaxDim; ++k) {
+          d[k] = xq[k] - ct[k];  // (components beyond I: 0 - 0)
+          d2 += d[k] * d[k];
+        }
+        phi_and_slope_d(sqrt(d2), order, phi, slope);
+#pragma unroll
+        for (int o = 0; o < kAdjMaxDim; ++o) {
+          acc[o] += phi * g[o];
+          a += g[o] * wt[o];
+        }
+        a *= slope;
+#pragma unroll
+        for (int k = 0; k < kAdjMaxDim; ++k) gcv[k] -= a * d[k];
+      } else {  // an affine row: x_qk (row T + k) or 1 (row T + I) in phi's place
+        double f = 1.0;
+#pragma unroll
+        for (int k = 0; k < kAdjMaxDim; ++k)
+          if (row - T == k && k < I) f = xq[k];
+#pragma unroll
+        for (int o = 0; o < kAdjMaxDim; ++o) acc[o] += f * g[o];
+      }
+    }
+#pragma unroll
+    for (int o = 0; o < kAdjMaxDim; ++o)
+      if (o < O) buf[tid * NV + o] = acc[o];
+#pragma unroll
+    for (int k = 0; k < kAdjMaxDim; ++k)
+      if (k < I) buf[tid * NV + O + k] = gcv[k];
+  }
+  __syncthreads();
+  // the slices' sums in slice order: thread j owns value v of row rr
+  double *pn = part + (n * gridDim.x / tiles + chunk) * ((int64_t)S * O + (int64_t)T * I);
+  for (int j = tid; j < rows * NV; j += kAdjRows) {
+    const int r = j / NV, v = j - r * NV, grow = tile * kAdjRows + r;
+    double sum = 0.0;
+    for (int sl = 0; sl < nsl; ++sl) sum += buf[(sl * rows + r) * NV + v];
+    if (v < O) pn[(int64_t)grow * O + v] = sum;
+    else if (grow < T) pn[(int64_t)S * O + (int64_t)grow * I + (v - O)] = sum;
+  }
+}
+
+// rhs (N, S, O) then g_c (N, T, I): each element the sum of its `chunks` partials, first to last
+__global__ void __launch_bounds__(256)
+spline_adjoint_sum_kernel(const double *__restrict__ part, int chunks, int64_t so, int64_t ti,
+                          double *__restrict__ rhs, double *__restrict__ gc) {
+  const int64_t n = blockIdx.y, per = so + ti;
+  const int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (e >= per) return;
+  const double *p = part + n * chunks * per + e;
+  double sum = 0.0;
+  for (int k = 0; k < chunks; ++k) sum += p[k * per];
+  if (e < so) rhs[n * so + e] = sum;
+  else gc[n * ti + (e - so)] = sum;
+}
+
+// g_x[q] = sum_t (G[q] . w[t]) slope(r_qt) (x_q - c_t) + v[:I] G[q]: lane = query, the centres in a loop
+// (spline_apply_kernel's structure and staging)
+template <bool STAGE>
+__global__ void __launch_bounds__(256)
+spline_adjoint_gx_kernel(const float *__restrict__ G, const float *__restrict__ c, const double *__restrict__ wv,
+                         const float *__restrict__ x, int T, int I, int O, int Q, int order,
+                         double *__restrict__ gx) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int64_t n = blockIdx.y;
+  const double *lw = wv + n * (int64_t)(T + I + 1) * O;
+  const float *lc = c + n * (int64_t)T * I;
+  if (STAGE) {
+    double *sw = reinterpret_cast<double *>(smem);
+    float *sc = reinterpret_cast<float *>(sw + (size_t)(T + I + 1) * O);
+    for (int i = (int)threadIdx.x; i < (T + I + 1) * O; i += (int)blockDim.x) sw[i] = lw[i];
+    for (int i = (int)threadIdx.x; i < T * I; i += (int)blockDim.x) sc[i] = lc[i];
+    __syncthreads();
+    lw = sw;
+    lc = sc;
+  }
+  const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (q >= Q) return;
+  double xq[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0}, g[kAdjMaxDim] = {0.0, 0.0, 0.0, 0.0}, out[kAdjMaxDim];
+#pragma unroll
+  for (int k = 0; k < kAdjMaxDim; ++k)
+    if (k < I) xq[k] = (double)x[(n * Q + q) * I + k];
+#pragma unroll
+  for (int o = 0; o < kAdjMaxDim; ++o)
+    if (o < O) g[o] = (double)G[(n * Q + q) * O + o];
+#pragma unroll
+  for (int k = 0; k < kAdjMaxDim; ++k) {
+    out[k] = 0.0;
+    if (k < I)
+      for (int o = 0; o < O; ++o) out[k] += g[o] * lw[(T + k) * O + o];
+  }
+  for (int t = 0; t < T; ++t) {
+    double d[kAdjMaxDim], d2 = 0.0, a = 0.0, phi, slope;
+#pragma unroll
+    for (int k = 0; k < kAdjMaxDim; ++k) {
+      d[k] = k < I ? xq[k] - (double)lc[t * I + k] : 0.0;
+      d2 += d[k] * d[k];
+    }
+    phi_and_slope_d(sqrt(d2), order, phi, slope);
+#pragma unroll
+    for (int o = 0; o < kAdjMaxDim; ++o)
+      if (o < O) a += g[o] * lw[t * O + o];
+    a *= slope;
+#pragma unroll
+    for (int k = 0; k < kAdjMaxDim; ++k) out[k] += a * d[k];
+  }
+#pragma unroll
+  for (int k = 0; k < kAdjMaxDim; ++k)
+    if (k < I) gx[(n * Q + q) * I + k] = out[k];
+}
+
 // warp_1d_grid (_img.py:268-303): one workgroup per batch element
 __global__ void __launch_bounds__(256)
 warp_1d_grid_kernel(const float *__restrict__ src, const float *__restrict__ flow,
@@ -279,6 +503,61 @@ int pdt_polyharmonic_spline(const float *train_points, const float *train_values
                         (hipStream_t)stream);
   if (rc != PDT_OK) return rc;
   return spline_apply(train_points, wv, query_points, N, T, I, O, Q, order, out, (hipStream_t)stream);
+}
+
+// the checks pdt_spline_eval_adjoint and its plan share
+static int eval_adjoint_check(int64_t N, int64_t T, int64_t I, int64_t O, int64_t Q, int order) {
+  if (N < 0 || T < 1 || I < 1 || O < 1 || Q < 0 || order < 1) return PDT_E_ARG;
+  if (I > pdt::kAdjMaxDim || O > pdt::kAdjMaxDim) return PDT_E_UNSUPPORTED;
+  if (N > 65535 || Q >= (1ll << 31) || T > (1ll << 20)) return PDT_E_TOO_LONG;
+  return PDT_OK;
+}
+
+int pdt_spline_eval_adjoint_plan(int64_t N, int64_t T, int64_t I, int64_t O, int64_t Q, int64_t *plan) {
+  if (const int rc = eval_adjoint_check(N, T, I, O, Q, 1)) return rc;
+  const pdt::AdjPlan p = pdt::adj_plan(T, I, O, Q);
+  if (plan) {
+    plan[0] = p.form;
+    plan[1] = (int64_t)p.chunks * p.tiles;                                // workgroups per batch element
+    plan[2] = N * p.partial_doubles * (int64_t)sizeof(double) + 64;      // workspace bytes
+    plan[3] = p.gx_staged;
+    plan[4] = p.nsl;
+    plan[5] = p.qper;
+  }
+  return p.form;
+}
+
+int pdt_spline_eval_adjoint(const float *grad_out, const float *train_points, const double *solution,
+                            const float *query_points, int64_t N, int64_t T, int64_t I, int64_t O, int64_t Q,
+                            int64_t H, int64_t W, int order, double *rhs, double *grad_points,
+                            double *grad_query, void *workspace, void *stream) {
+  using namespace pdt;
+  if (const int rc = eval_adjoint_check(N, T, I, O, Q, order)) return rc;
+  if (!query_points && (I != 2 || H < 0 || W < 0 || H * W != Q || grad_query)) return PDT_E_ARG;
+  if (N == 0) return PDT_OK;
+  if (!train_points || !solution || !rhs || !grad_points || !workspace || (Q > 0 && !grad_out)) return PDT_E_ARG;
+  const AdjPlan p = adj_plan(T, I, O, Q);
+  const int64_t S = T + I + 1;
+  double *part = reinterpret_cast<double *>(workspace);
+  hipLaunchKernelGGL(spline_adjoint_partial_kernel, dim3((unsigned)(p.chunks * p.tiles), (unsigned)N), dim3(kAdjRows),
+                     0, (hipStream_t)stream, grad_out, train_points, solution, query_points, (int)T, (int)I, (int)O,
+                     (int)Q, (int)(W > 0 ? W : 1), order, p.nsl, p.tiles, p.qper, part);
+  const int64_t per = S * O + T * I;
+  hipLaunchKernelGGL(spline_adjoint_sum_kernel, dim3((unsigned)((per + 255) / 256), (unsigned)N), dim3(256), 0,
+                     (hipStream_t)stream, part, p.chunks, S * O, T * I, rhs, grad_points);
+  if (grad_query && Q > 0) {
+    const dim3 grid((unsigned)((Q + 255) / 256), (unsigned)N);
+    if (p.gx_staged) {
+      const size_t smem = spline_apply_lds_bytes(T, I, O);
+      if (const int rc = set_lds(spline_adjoint_gx_kernel<true>, smem)) return rc;
+      hipLaunchKernelGGL(spline_adjoint_gx_kernel<true>, grid, dim3(256), smem, (hipStream_t)stream, grad_out,
+                         train_points, solution, query_points, (int)T, (int)I, (int)O, (int)Q, order, grad_query);
+    } else {
+      hipLaunchKernelGGL(spline_adjoint_gx_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, grad_out,
+                         train_points, solution, query_points, (int)T, (int)I, (int)O, (int)Q, order, grad_query);
+    }
+  }
+  return (int)hipGetLastError();
 }
 
 int pdt_warp_1d_grid(const float *src, const float *flow, const float *lengths, int64_t N, int64_t T,

@@ -28,7 +28,9 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # pdt_relaxed_backward_workspace_bytes, pdt_relaxed_gumbel_backward, pdt_relaxed_bernoulli_backward) and the
 # host-only plans of BeamSearch's kernels (pdt_beam_search_step_plan, pdt_beam_search_table_plan) and the fused
 # ConcatSoftAttention score (pdt_concat_score, pdt_concat_score_backward, pdt_concat_score_workspace_bytes,
-# pdt_concat_score_plan).
+# pdt_concat_score_plan) and the warps' position gradients with the spline evaluation's adjoint
+# (pdt_dense_image_warp_flow_backward[_f64], pdt_sparse_image_warp_position_backward[_f64],
+# pdt_spline_eval_adjoint, pdt_spline_eval_adjoint_plan).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -191,6 +193,21 @@ SIGNATURES = {
     "pdt_sparse_image_warp_backward_f64": (
         _INT,
         [_P, _P, _P, _I64, _I64, _I64, _I64, _I64, _INT, _F, _INT, _INT, _INT, _P, _P, _P],
+    ),
+    # gradients of the warps with respect to flow / spline values, and the spline evaluation's adjoint
+    "pdt_dense_image_warp_flow_backward": (_INT, [_P, _P, _P, _I64, _I64, _I64, _I64, _INT, _INT, _INT, _P, _P]),
+    "pdt_dense_image_warp_flow_backward_f64": (_INT, [_P, _P, _P, _I64, _I64, _I64, _I64, _INT, _INT, _INT, _P, _P]),
+    "pdt_sparse_image_warp_position_backward": (
+        _INT,
+        [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _INT, _INT, _INT, _INT, _P, _INT, _P, _P, _P],
+    ),
+    "pdt_sparse_image_warp_position_backward_f64": (
+        _INT,
+        [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _INT, _INT, _INT, _INT, _P, _INT, _P, _P, _P],
+    ),
+    "pdt_spline_eval_adjoint_plan": (_INT, [_I64, _I64, _I64, _I64, _I64, _P]),
+    "pdt_spline_eval_adjoint": (
+        _INT, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _P, _P, _P, _P, _P],
     ),
     "pdt_lookup_lm_log_probs": (
         _INT,

@@ -4,7 +4,12 @@ Host-side mirror of the reference's ``_img.py`` for the operators on the hot pat
 (``polyharmonic_spline``, ``warp_1d_grid``, ``dense_image_warp``, ``sparse_image_warp``,
 ``spec_augment*`` and their Modules).  Kernels: ``csrc/spline.hip``, ``csrc/spec_augment.hip``, ``csrc/image_warp.hip`` through the C ABI
 (``include/pdt_amd.h``).  ``spec_augment_apply_parameters`` and the image warps are
-differentiable with respect to the features / image (bilinear scatter in the backward pass).
+differentiable with respect to the features / image (bilinear scatter in the backward pass); the image
+warps also with respect to the flow / the control points, and the spline with respect to points, values
+and queries (``dense_image_warp_flow_backward``, ``sparse_image_warp_points_backward``,
+``spline_eval_adjoint``: HIP kernels; the torch bodies they replaced stay as ``_dense_flow_grad_torch``,
+``_sparse_points_grad_torch`` and ``_spline_eval_adjoint_torch`` for the sizes the kernels refuse and for
+profiles/tools/time_warp_grads.py -- there is no run-time switch).
 """
 import functools
 import math
@@ -130,6 +135,140 @@ def _spline_solve(c: torch.Tensor, f: torch.Tensor, tail: Optional[torch.Tensor]
     return sol
 
 
+def _phi_and_slope(r: torch.Tensor, order: int):
+    """phi(r) and phi'(r) / r (zero where r = 0: the direction vector vanishes there)."""
+    eps = float(torch.finfo(torch.float).eps)
+    pos = r > 0
+    safe = torch.where(pos, r, torch.ones_like(r))
+    if order % 2:
+        phi = r**order
+        slope = order * safe ** (order - 2)
+    else:
+        lg = torch.log(safe.clamp(min=eps))
+        phi = r**order * lg
+        inner = torch.where(safe > eps, order * lg + 1.0, torch.full_like(lg, order * math.log(eps)))
+        slope = safe ** (order - 2) * inner
+    return phi, torch.where(pos, slope, torch.zeros_like(slope))
+
+
+def _spline_eval_adjoint_torch(G: torch.Tensor, c: torch.Tensor, sol: torch.Tensor, x: torch.Tensor, order: int,
+                               need_gx: bool):  # fmt: skip
+    """The query-sized sums of the spline's backward as elementwise torch ops in float64 over (N, Q, T, I):
+    the shapes csrc/spline.hip's reduction refuses (I or O above 4), and the other contestant of
+    profiles/tools/time_warp_grads.py.  Returns what ``_spline_eval_adjoint`` returns."""
+    d = torch.double
+    T, I = c.shape[1], c.shape[2]
+    G, cd, xd = G.to(d), c.to(d), x.to(d)
+    w, v = sol[:, :T], sol[:, T:]
+    dxc = xd.unsqueeze(2) - cd.unsqueeze(1)  # (N, Q, T, I)
+    phi_xc, slope_xc = _phi_and_slope(dxc.norm(dim=3), order)
+    x1 = torch.cat([xd, torch.ones_like(xd[..., :1])], 2)
+    g_sol = torch.cat([phi_xc.transpose(1, 2) @ G, x1.transpose(1, 2) @ G], 1)  # (N, T+I+1, O)
+    g_phi = (G @ w.transpose(1, 2)) * slope_xc  # (N, Q, T): dL/dPhi * phi'/r
+    g_c = -(g_phi.unsqueeze(3) * dxc).sum(1)
+    g_x = (g_phi.unsqueeze(3) * dxc).sum(2) + G @ v[:, :I].transpose(1, 2) if need_gx else None
+    return g_sol, g_c, g_x
+
+
+def _pixel_lattice(N: int, H: int, W: int, device) -> torch.Tensor:
+    """(N, H*W, 2) float queries (x = w, y = h) of an H x W image, row-major."""
+    hh, ww = torch.meshgrid(
+        torch.arange(H, dtype=torch.float, device=device), torch.arange(W, dtype=torch.float, device=device),
+        indexing="ij",
+    )  # fmt: skip
+    return torch.stack([ww.flatten(), hh.flatten()], 1).unsqueeze(0).expand(N, H * W, 2)
+
+
+@custom_op("pydrobert_amd::spline_eval_adjoint", mutates_args=())
+def _spline_eval_adjoint_op(
+    grad_out: torch.Tensor,
+    train_points: torch.Tensor,
+    solution: torch.Tensor,
+    query_points: Optional[torch.Tensor],
+    height: int,
+    width: int,
+    order: int,
+    need_query_grad: bool,
+) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The query-sized half of the spline's backward (csrc/spline.hip: pdt_spline_eval_adjoint), float64:
+    ``(rhs (N, T+I+1, O), grad_points (N, T, I), grad_query (N, Q, I))`` for ``grad_out`` (N, Q, O), the
+    centres ``train_points`` and the float64 ``solution`` (N, T+I+1, O) of the spline.  ``query_points``
+    None: the pixel lattice of a ``height x width`` image.  ``grad_query`` has zero elements unless
+    ``need_query_grad``.  I, O <= 4."""
+    device = _cabi.require_hip(grad_out, train_points, solution, query_points)
+    G, c = _f32c(grad_out), _f32c(train_points)
+    x = None if query_points is None else _f32c(query_points)
+    sol = solution.detach().contiguous()
+    if sol.dtype != torch.double:
+        raise RuntimeError("solution must be float64")
+    N, T, I = c.shape
+    Q, O = G.shape[1], G.shape[2]
+    if sol.shape != (N, T + I + 1, O) or G.shape[0] != N or (x is not None and x.shape != (N, Q, I)):
+        raise RuntimeError("grad_out, train_points, solution and query_points have inconsistent shapes")
+    if need_query_grad and x is None:
+        raise RuntimeError("the pixel lattice has no gradient")
+    L = _cabi.lib()
+    plan = (_cabi._I64 * 6)()
+    _cabi.check(min(L.pdt_spline_eval_adjoint_plan(N, T, I, O, Q, plan), 0), "pdt_spline_eval_adjoint_plan")
+    with torch.cuda.device(device):
+        rhs = torch.empty((N, T + I + 1, O), device=device, dtype=torch.double)
+        g_c = torch.empty((N, T, I), device=device, dtype=torch.double)
+        g_x = torch.empty((N, Q, I) if need_query_grad else (0,), device=device, dtype=torch.double)
+        ws = torch.empty((int(plan[2]),), device=device, dtype=torch.uint8)
+        rc = L.pdt_spline_eval_adjoint(
+            _cabi.ptr(G), _cabi.ptr(c), _cabi.ptr(sol), _cabi.ptr(x), N, T, I, O, Q, int(height), int(width),
+            int(order), _cabi.ptr(rhs), _cabi.ptr(g_c), _cabi.ptr(g_x) if need_query_grad else None,
+            _cabi.ptr(ws), _cabi.stream_ptr(device),
+        )  # fmt: skip
+    _cabi.check(rc, "pdt_spline_eval_adjoint")
+    return rhs, g_c, g_x
+
+
+@_spline_eval_adjoint_op.register_fake
+def _(grad_out, train_points, solution, query_points, height, width, order, need_query_grad):
+    N, T, I = train_points.shape
+    Q, O = grad_out.shape[1], grad_out.shape[2]
+    d = torch.double
+    return (
+        grad_out.new_empty((N, T + I + 1, O), dtype=d),
+        grad_out.new_empty((N, T, I), dtype=d),
+        grad_out.new_empty((N, Q, I) if need_query_grad else (0,), dtype=d),
+    )
+
+
+_SPLINE_ADJOINT_MAX_DIM = 4  # csrc/spline.hip: kAdjMaxDim
+
+
+def _spline_eval_adjoint(G, c, sol, x, H: int, W: int, order: int, need_gx: bool):
+    """(g_sol, g_c, g_x): the adjoint system's right-hand side, the evaluation's share of the centres'
+    gradient and the queries' gradient (None unless ``need_gx``), float64.  ``x`` None: the H x W pixel
+    lattice.  The HIP reduction where it serves the sizes (I, O <= 4), the torch sums beyond."""
+    if c.shape[2] <= _SPLINE_ADJOINT_MAX_DIM and G.shape[2] <= _SPLINE_ADJOINT_MAX_DIM:
+        g_sol, g_c, g_x = torch.ops.pydrobert_amd.spline_eval_adjoint(G, c, sol, x, H, W, order, need_gx)
+        return g_sol, g_c, (g_x if need_gx else None)
+    if x is None:
+        x = _pixel_lattice(c.shape[0], H, W, c.device)
+    return _spline_eval_adjoint_torch(G, c, sol, x, order, need_gx)
+
+
+def _spline_system_adjoint(c: torch.Tensor, sol: torch.Tensor, g_sol: torch.Tensor, order: int, reg: float):
+    """(g_c, g_f) through the spline's system for the right-hand side ``g_sol`` of its adjoint: one solve
+    (the matrix is symmetric), then dL/dM = -lam sol^T chained into the centres -- small torch ops over
+    (N, T, T)."""
+    T, I = c.shape[1], c.shape[2]
+    cd = c.to(torch.double)
+    w, v = sol[:, :T], sol[:, T:]
+    lam = _spline_solve(c, g_sol[:, :T].float().contiguous(), g_sol[:, T:].float().contiguous(), order, reg)
+    lam_w, lam_v = lam[:, :T], lam[:, T:]
+    dcc = cd.unsqueeze(2) - cd.unsqueeze(1)  # (N, T, T, I)
+    _, slope_cc = _phi_and_slope(dcc.norm(dim=3), order)
+    g_A = -(lam_w @ w.transpose(1, 2))
+    g_A = (g_A + g_A.transpose(1, 2)) * slope_cc
+    g_c = (g_A.unsqueeze(3) * dcc).sum(2)
+    g_B = -(lam_w @ v.transpose(1, 2) + w @ lam_v.transpose(1, 2))  # (N, T, I+1)
+    return g_c + g_B[..., :I], lam_w
+
+
 @custom_op("pydrobert_amd::polyharmonic_spline_backward", mutates_args=())
 def _polyharmonic_spline_backward_op(
     grad_out: torch.Tensor,
@@ -145,51 +284,12 @@ def _polyharmonic_spline_backward_op(
     the adjoint system M lam = [Phi^T G; [x 1]^T G] is solved by the same kernel (float64), the
     rest are the chain rules of phi(|x - c|) and phi(|c_i - c_j|) -- elementwise / matmul device
     ops over (N, Q, T) and (N, T, T)."""
-    device = _cabi.require_hip(grad_out, train_points, train_values, query_points)
+    _cabi.require_hip(grad_out, train_points, train_values, query_points)
     c, f, x = _f32c(train_points), _f32c(train_values), _f32c(query_points)
-    N, T, I = c.shape
-    d = torch.double
-    G = grad_out.detach().to(d)
-    cd, xd = c.to(d), x.to(d)
-    eps = float(torch.finfo(torch.float).eps)
-
-    def phi_and_slope(r):
-        """phi(r) and phi'(r) / r (zero where r = 0: the direction vector vanishes there)."""
-        pos = r > 0
-        safe = torch.where(pos, r, torch.ones_like(r))
-        if order % 2:
-            phi = r**order
-            slope = order * safe ** (order - 2)
-        else:
-            lg = torch.log(safe.clamp(min=eps))
-            phi = r**order * lg
-            inner = torch.where(safe > eps, order * lg + 1.0, torch.full_like(lg, order * math.log(eps)))
-            slope = safe ** (order - 2) * inner
-        return phi, torch.where(pos, slope, torch.zeros_like(slope))
-
     sol = _spline_solve(c, f, None, order, regularization_weight)  # (N, T+I+1, O)
-    w, v = sol[:, :T], sol[:, T:]
-    dxc = xd.unsqueeze(2) - cd.unsqueeze(1)  # (N, Q, T, I)
-    r_xc = dxc.norm(dim=3)
-    phi_xc, slope_xc = phi_and_slope(r_xc)
-    x1 = torch.cat([xd, torch.ones_like(xd[..., :1])], 2)
-    g_sol = torch.cat([phi_xc.transpose(1, 2) @ G, x1.transpose(1, 2) @ G], 1)  # (N, T+I+1, O)
-    lam = _spline_solve(c, g_sol[:, :T].float().contiguous(), g_sol[:, T:].float().contiguous(), order,
-                        regularization_weight)  # fmt: skip
-    lam_w, lam_v = lam[:, :T], lam[:, T:]
-    g_f = lam_w
-    # through the evaluation: out = Phi(x, c) w + [x 1] v
-    g_phi = (G @ w.transpose(1, 2)) * slope_xc  # (N, Q, T): dL/dPhi * phi'/r
-    g_x = (g_phi.unsqueeze(3) * dxc).sum(2) + G @ v[:, :I].transpose(1, 2)
-    g_c = -(g_phi.unsqueeze(3) * dxc).sum(1)
-    # through the system: dL/dM = -lam sol^T
-    dcc = cd.unsqueeze(2) - cd.unsqueeze(1)  # (N, T, T, I)
-    _, slope_cc = phi_and_slope(dcc.norm(dim=3))
-    g_A = -(lam_w @ w.transpose(1, 2))
-    g_A = (g_A + g_A.transpose(1, 2)) * slope_cc
-    g_c = g_c + (g_A.unsqueeze(3) * dcc).sum(2)
-    g_B = -(lam_w @ v.transpose(1, 2) + w @ lam_v.transpose(1, 2))  # (N, T, I+1)
-    g_c = g_c + g_B[..., :I]
+    g_sol, g_c, g_x = _spline_eval_adjoint(grad_out.detach(), c, sol, x, 0, 0, order, True)
+    g_sys, g_f = _spline_system_adjoint(c, sol, g_sol, order, regularization_weight)
+    g_c = g_c + g_sys
     return g_c.to(train_points.dtype), g_f.to(train_values.dtype), g_x.to(query_points.dtype)
 
 
@@ -392,23 +492,69 @@ def _dense_backward(ctx, grad_out):
         g = torch.ops.pydrobert_amd.dense_image_warp_backward(grad_out, flow, indexing, mode, padding_mode)
     g_flow = None
     if ctx.needs_flow and ctx.needs_input_grad[1]:
-        # the derivative of the bilinear taps with respect to the sampling position: torch's own
-        # grid_sample adjoint on the device, the graph the reference differentiates (:436)
-        image = ctx.saved_tensors[1]
-        with torch.enable_grad():
-            fl = flow.detach().float().requires_grad_(True)
-            grid = _sampling_grid_from_flow(fl, indexing, image.shape[2], image.shape[3])
-            out = torch.nn.functional.grid_sample(
-                image.detach().float(), grid, mode=mode, padding_mode=padding_mode, align_corners=False
-            )
-            (g_flow,) = torch.autograd.grad(out, fl, grad_out.float())
-        g_flow = g_flow.to(flow.dtype)
+        # the derivative of the bilinear taps with respect to the sampling position (csrc/image_warp.hip,
+        # WARP_POSITION): what the reference's graph differentiates through grid_sample's grid (:436)
+        g_flow = torch.ops.pydrobert_amd.dense_image_warp_flow_backward(
+            grad_out, ctx.saved_tensors[1], flow, indexing, mode, padding_mode
+        )
     return g, g_flow, None, None, None
+
+
+def _dense_flow_grad_torch(grad_out, image, flow, indexing, mode, padding_mode):
+    """The flow's gradient through torch's own grid_sample adjoint on the device, in float32 whatever the
+    image's type: not on any operator's path -- the other contestant of profiles/tools/time_warp_grads.py."""
+    with torch.enable_grad():
+        fl = flow.detach().float().requires_grad_(True)
+        grid = _sampling_grid_from_flow(fl, indexing, image.shape[2], image.shape[3])
+        out = torch.nn.functional.grid_sample(
+            image.detach().float(), grid, mode=mode, padding_mode=padding_mode, align_corners=False
+        )
+        (g_flow,) = torch.autograd.grad(out, fl, grad_out.float())
+    return g_flow.to(flow.dtype)
+
+
+@custom_op("pydrobert_amd::dense_image_warp_flow_backward", mutates_args=())
+def _dense_image_warp_flow_backward_op(
+    grad_out: torch.Tensor, image: torch.Tensor, flow: torch.Tensor, indexing: str, mode: str, padding_mode: str
+) -> torch.Tensor:
+    """Gradient of ``dense_image_warp`` with respect to the flow (csrc/image_warp.hip, WARP_POSITION), in
+    the image's type from the grid on, like the forward."""
+    device = _cabi.require_hip(grad_out, image, flow)
+    N, C, H, W = image.shape
+    if mode == "nearest":  # (piecewise constant in the flow: no launch)
+        return torch.zeros_like(flow)
+    (img, sfx), fl = _pixels(image), _f32c(flow)
+    g = grad_out.detach().to(img.dtype).contiguous()
+    with torch.cuda.device(device):
+        grad = torch.empty((N, H, W, 2), device=device, dtype=torch.float)
+        rc = getattr(_cabi.lib(), "pdt_dense_image_warp_flow_backward" + sfx)(
+            _cabi.ptr(g), _cabi.ptr(img), _cabi.ptr(fl), N, C, H, W, int(indexing == "hw"), _MODES[mode],
+            _PADDINGS[padding_mode], _cabi.ptr(grad), _cabi.stream_ptr(device),
+        )  # fmt: skip
+    _cabi.check(rc, "pdt_dense_image_warp_flow_backward")
+    return grad.to(flow.dtype)
+
+
+@_dense_image_warp_flow_backward_op.register_fake
+def _(grad_out, image, flow, indexing, mode, padding_mode):
+    return flow.new_empty(flow.shape)
+
+
+def _no_double_backward(ctx, *grads):
+    raise RuntimeError(
+        "pydrobert_amd image warps: double backward is not supported (the gradient kernels are not differentiable)"
+    )
+
+
+def _setup_nothing(ctx, inputs, output):
+    pass
 
 
 register_autograd(
     "pydrobert_amd::dense_image_warp", _dense_backward, setup_context=_dense_setup_context
 )
+register_autograd("pydrobert_amd::dense_image_warp_flow_backward", _no_double_backward, setup_context=_setup_nothing)
+register_autograd("pydrobert_amd::spline_eval_adjoint", _no_double_backward, setup_context=_setup_nothing)
 
 
 def dense_image_warp(
@@ -578,51 +724,131 @@ def _sparse_backward(ctx, grad_warped, grad_flow):
             grad_warped, source_points, dest_points, *ctx.cfg
         )
     g_src = g_dst = None
-    if ctx.points_need_grad:
-        # control points: the spline (its own backward kernel path) chained into the gather's
-        # position derivative, as the reference's graph does (_img.py:561-585, :633-655)
-        image = ctx.saved_tensors[2]
-        indexing, order, reg, pinned, mode, padding, include_flow = ctx.cfg
-        N, C, H, W = image.shape
-        if source_points.shape[1]:
-            with torch.enable_grad():
-                s0 = source_points.detach().float().requires_grad_(True)
-                d0 = dest_points.detach().float().requires_grad_(True)
-                src, dst = (s0.flip(-1), d0.flip(-1)) if indexing == "hw" else (s0, d0)
-                if pinned > 0:
-                    pp = _pinned_points(pinned, W, H, N, image.device)
-                    src, dst = torch.cat([src, pp], 1), torch.cat([dst, pp], 1)
-                hh, ww = torch.meshgrid(
-                    torch.arange(H, dtype=torch.float, device=image.device),
-                    torch.arange(W, dtype=torch.float, device=image.device), indexing="ij",
-                )  # fmt: skip
-                query = torch.stack([ww.flatten(), hh.flatten()], 1).unsqueeze(0).expand(N, H * W, 2)
-                size = torch.tensor([W, H], dtype=torch.float, device=image.device)
-                outs, grads = [], []
-                if include_flow:
-                    flow = torch.ops.pydrobert_amd.polyharmonic_spline(dst, dst - src, query, order, reg)
-                    flow = flow.view(N, H, W, 2)
-                    grid = _sampling_grid_from_flow(flow, "wh", H, W)
-                    if grad_flow is not None:
-                        outs.append(flow.flip(-1) if indexing == "hw" else flow)
-                        grads.append(grad_flow.float())
-                else:
-                    grid = torch.ops.pydrobert_amd.polyharmonic_spline(
-                        dst, (2.0 * src + 1.0) / size - 1.0, query, order, reg
-                    ).view(N, H, W, 2)
-                warped = torch.nn.functional.grid_sample(
-                    image.detach().float(), grid, mode=mode, padding_mode=padding, align_corners=False
-                )
-                outs.append(warped)
-                grads.append(grad_warped.float())
-                g_src, g_dst = torch.autograd.grad(outs, [s0, d0], grads, allow_unused=True)
-            g_src = None if g_src is None else g_src.to(source_points.dtype)
-            g_dst = None if g_dst is None else g_dst.to(dest_points.dtype)
+    if ctx.points_need_grad and source_points.shape[1]:
+        # control points: the gather's position derivative chained into the spline's adjoint, as the
+        # reference's graph does (_img.py:561-585, :633-655)
+        include_flow = ctx.cfg[-1]
+        g_src, g_dst = torch.ops.pydrobert_amd.sparse_image_warp_points_backward(
+            grad_warped, grad_flow if include_flow else None, ctx.saved_tensors[2], source_points, dest_points,
+            *ctx.cfg
+        )
     return (g, g_src, g_dst) + (None,) * 7
+
+
+def _sparse_points_grad_torch(grad_warped, grad_flow, image, source_points, dest_points, indexing, order, reg,
+                              pinned, mode, padding, include_flow):  # fmt: skip
+    """The control points' gradients by autograd through the spline at every pixel and torch's grid_sample
+    on the device (float32): not on any operator's path -- the other contestant of
+    profiles/tools/time_warp_grads.py.  Its spline backward takes the torch sums over (N, H*W, T, 2)."""
+    N, C, H, W = image.shape
+    with torch.enable_grad():
+        s0 = source_points.detach().float().requires_grad_(True)
+        d0 = dest_points.detach().float().requires_grad_(True)
+        src, dst = (s0.flip(-1), d0.flip(-1)) if indexing == "hw" else (s0, d0)
+        if pinned > 0:
+            pp = _pinned_points(pinned, W, H, N, image.device)
+            src, dst = torch.cat([src, pp], 1), torch.cat([dst, pp], 1)
+        query = _pixel_lattice(N, H, W, image.device)
+        size = torch.tensor([W, H], dtype=torch.float, device=image.device)
+        vals = dst - src if include_flow else (2.0 * src + 1.0) / size - 1.0
+        c, f = dst.detach().contiguous(), vals.detach().contiguous()
+        sol = _spline_solve(c, f, None, order, reg)
+        out = torch.ops.pydrobert_amd.polyharmonic_spline(c, f, query, order, reg).view(N, H, W, 2)
+        out.requires_grad_(True)
+        outs, grads = [], []
+        if include_flow:
+            grid = _sampling_grid_from_flow(out, "wh", H, W)
+            if grad_flow is not None:
+                outs.append(out.flip(-1) if indexing == "hw" else out)
+                grads.append(grad_flow.float())
+        else:
+            grid = out
+        warped = torch.nn.functional.grid_sample(
+            image.detach().float(), grid, mode=mode, padding_mode=padding, align_corners=False
+        )
+        outs.append(warped)
+        grads.append(grad_warped.float())
+        (G,) = torch.autograd.grad(outs, [out], grads)
+        g_sol, g_c, _ = _spline_eval_adjoint_torch(G.reshape(N, H * W, 2), c, sol, query, order, False)
+        g_sys, g_f = _spline_system_adjoint(c, sol, g_sol, order, reg)
+        g_src, g_dst = torch.autograd.grad([dst, vals], [s0, d0], [(g_c + g_sys).float(), g_f.float()],
+                                           allow_unused=True)  # fmt: skip
+    g_src = torch.zeros_like(source_points) if g_src is None else g_src.to(source_points.dtype)
+    g_dst = torch.zeros_like(dest_points) if g_dst is None else g_dst.to(dest_points.dtype)
+    return g_src, g_dst
+
+
+@custom_op("pydrobert_amd::sparse_image_warp_points_backward", mutates_args=())
+def _sparse_image_warp_points_backward_op(
+    grad_warped: torch.Tensor,
+    grad_flow: Optional[torch.Tensor],
+    image: torch.Tensor,
+    source_points: torch.Tensor,
+    dest_points: torch.Tensor,
+    indexing: str,
+    field_interpolation_order: int,
+    field_regularization_weight: float,
+    pinned_boundary_points: int,
+    dense_interpolation_mode: str,
+    dense_padding_mode: str,
+    include_flow: bool,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Gradients of ``sparse_image_warp`` with respect to ``(source_points, dest_points)``: one solve, the
+    position-gradient kernel (csrc/image_warp.hip, WARP_POSITION; ``grad_flow``, the gradient of the
+    returned flow, is added there), the spline evaluation's adjoint over the pixel lattice
+    (csrc/spline.hip: pdt_spline_eval_adjoint), one adjoint solve, the (T, T) system terms, and the chain
+    back through the spline's values, the pinned points (no gradient) and ``indexing``."""
+    order, reg = int(field_interpolation_order), float(field_regularization_weight)
+    device, pts, vals, Mp = _sparse_prepare(
+        image, source_points, dest_points, indexing, pinned_boundary_points, include_flow
+    )
+    M = source_points.shape[1]
+    if Mp == 0:
+        return torch.zeros_like(source_points), torch.zeros_like(dest_points)
+    N, C, H, W = image.shape
+    if grad_flow is not None and not include_flow:
+        raise RuntimeError("grad_flow needs include_flow")
+    if dense_interpolation_mode == "nearest" and grad_flow is None:  # (no sample moves with its position)
+        return torch.zeros_like(source_points), torch.zeros_like(dest_points)
+    img, sfx = _pixels(image)
+    g = grad_warped.detach().to(img.dtype).contiguous()
+    gf = None if grad_flow is None else _f32c(grad_flow)
+    L = _cabi.lib()
+    sol = _spline_solve(pts, vals, None, order, reg)  # (N, Mp + 3, 2)
+    with torch.cuda.device(device):
+        G = torch.empty((N, H, W, 2), device=device, dtype=torch.float)
+        ws = torch.empty((int(L.pdt_spline_workspace_bytes(N, Mp, 2, 2)),), device=device, dtype=torch.uint8)
+        rc = getattr(L, "pdt_sparse_image_warp_position_backward" + sfx)(
+            _cabi.ptr(g), _cabi.ptr(img), _cabi.ptr(pts), _cabi.ptr(sol), N, C, H, W, Mp, order,
+            int(not include_flow), _MODES[dense_interpolation_mode], _PADDINGS[dense_padding_mode],
+            _cabi.ptr(gf), int(indexing == "hw"), _cabi.ptr(G), _cabi.ptr(ws), _cabi.stream_ptr(device),
+        )  # fmt: skip
+    _cabi.check(rc, "pdt_sparse_image_warp_position_backward")
+    g_sol, g_c, _ = _spline_eval_adjoint(G.view(N, H * W, 2), pts, sol, None, H, W, order, False)
+    g_sys, g_f = _spline_system_adjoint(pts, sol, g_sol, order, reg)
+    g_c = (g_c + g_sys)[:, :M]  # (the pinned points are constants)
+    g_f = g_f[:, :M]
+    if include_flow:  # values = dst - src
+        g_src, g_dst = -g_f, g_c + g_f
+    else:  # values = (2 src + 1) / size - 1
+        g_src, g_dst = g_f * (2.0 / _wh_const(W, H, device).double()), g_c
+    if indexing == "hw":
+        g_src, g_dst = g_src.flip(-1), g_dst.flip(-1)
+    return g_src.to(source_points.dtype).contiguous(), g_dst.to(dest_points.dtype).contiguous()
+
+
+@_sparse_image_warp_points_backward_op.register_fake
+def _(grad_warped, grad_flow, image, source_points, dest_points, indexing, field_interpolation_order,
+      field_regularization_weight, pinned_boundary_points, dense_interpolation_mode, dense_padding_mode,
+      include_flow):  # fmt: skip
+    return torch.empty_like(source_points), torch.empty_like(dest_points)
 
 
 register_autograd(
     "pydrobert_amd::sparse_image_warp", _sparse_backward, setup_context=_sparse_setup_context
+)
+register_autograd(
+    "pydrobert_amd::sparse_image_warp_points_backward", _no_double_backward, setup_context=_setup_nothing
 )
 
 

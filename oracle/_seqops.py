@@ -68,7 +68,7 @@ def fill_after_eos(tokens, eos, dim=0, fill=None, value=None):
     out = tok if value is None else _np(value)
     hit = tok == eos
     seen = np.cumsum(hit, axis=dim) - hit  # eos occurrences at earlier positions (dim: of the TOKENS)
-    fill_ = float(eos) if fill is None else fill
+    fill_ = eos if fill is None else fill  # (eos as the integer it is: a float does not hold every int64)
     # masked_fill broadcasts the mask and the filled tensor against each other
     shape = np.broadcast_shapes(out.shape, seen.shape)
     out = np.broadcast_to(out, shape).copy()

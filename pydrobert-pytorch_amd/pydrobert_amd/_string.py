@@ -68,8 +68,12 @@ def _fill_after_eos_op(tokens: torch.Tensor, eos: int, dim: int, fill: float, va
         raise RuntimeError("fill_after_eos: complex values are not supported")
     out = torch.empty_like(val)
     # the fill value converted the way masked_fill converts its scalar, then its raw bits
-    one = torch.full((1,), fill, dtype=val.dtype)
-    bits = int(one.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[val.element_size()]).item())
+    if val.dtype == torch.long and fill == float(eos) and -(2**63) <= eos < 2**63:
+        # eos itself (the default fill): a double does not hold every int64, masked_fill's integer scalar does
+        bits = int(eos)
+    else:
+        one = torch.full((1,), fill, dtype=val.dtype)
+        bits = int(one.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[val.element_size()]).item())
     outer = 1
     for d in range(dim):
         outer *= tok.shape[d]

@@ -18,24 +18,10 @@ from pydrobert_amd._lm import SequentialLanguageModel
 
 from _lm_fixtures import random_dicts
 from _toy_lm import CounterLM, ScriptableBigramLM
+from _walk_plan import _choose, rule, u_inside  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-
-def rule(x, u):
-    x = np.asarray(x, np.float64)
-    w = np.exp(x - x.max())
-    P = np.cumsum(w)
-    hit = np.nonzero((P > u * P[-1]) & (w > 0))[0]
-    return int(hit[0]) if hit.size else int(np.nonzero(w > 0)[0][-1])
-
-
-def u_inside(x, tok, frac):
-    """A uniform whose draw from row x is token ``tok``: ``frac`` of the way through its interval."""
-    x = np.asarray(x, np.float64)
-    w = np.exp(x - x.max())
-    return (w[:tok].sum() + frac * w[tok]) / w.sum()
 
 
 def _rows(rng, N, V):
@@ -50,18 +36,6 @@ def _rows(rng, N, V):
         x[n] = -np.inf
         x[n, rng.integers(V)] = 0.0
     return x.astype(np.float32)
-
-
-def _choose(rng, x):
-    """(token, u) per row: a token of at least 5e-4 of the row's mass, u in its middle 60%."""
-    toks, us = [], []
-    for row in x:
-        w = np.exp(row.astype(np.float64) - row.max())
-        ok = np.nonzero(w / w.sum() >= 5e-4)[0]
-        k = int(rng.choice(ok))
-        toks.append(k)
-        us.append(u_inside(row, k, rng.uniform(0.2, 0.8)))
-    return np.array(toks), np.array(us, np.float32)
 
 
 def _expected_y(y_prev, lens, tok):

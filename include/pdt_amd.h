@@ -225,7 +225,8 @@ int pdt_ctc_lm_table_search(const float *logits, int64_t T, int64_t N, int64_t V
  * (reference _decoding.py:1064-1202; the per-frame step is ctc_prefix_search_advance,
  * :636-934; the softmax of :1093 is fused).
  *
- *   logits (T, N, V + 1) float32 through element strides, blank = index V.
+ *   logits (T, N, V + 1) float32 (float16 / bfloat16: the _elem entry point below) through element
+ *          strides, blank = index V.
  *   lens   (N,) int64 or NULL (all T).  S = number of rows of y = max(lens) (T if NULL).
  *   y      (S, N, width) int64 contiguous; every element is written (rows beyond a prefix's
  *          length are 0; the reference leaves them undefined);
@@ -255,10 +256,31 @@ int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, 
                           void *workspace, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Logits of float16 / bfloat16 (and float32) without a float32 copy: the _elem entry points.
+ * Each takes the arguments of its sibling plus the element type of the logits -- and, in
+ * pdt_sequence_log_probs_backward_elem, of grad_logits:
+ *   elem  0 float32 (what the sibling forwards with), 2 float16, 3 bfloat16;
+ *         1 (float64) returns PDT_E_UNSUPPORTED, any other value PDT_E_ARG.
+ * A half element is widened to float32, exactly, where the kernel loads it, and the arithmetic is
+ * the float32 kernel's: every output has the bits the sibling gives on the widened tensor.
+ * Strides stay element strides, rows need no alignment beyond the element's.  The other tensors,
+ * y_probs / max_out / out / grad_out among them, are float32 as before; grad_logits is written in
+ * the element type, rounded to nearest even.  Workspace sizes do not depend on the element type.
+ * The same shape takes the same kernel form for every element type; with rows held in registers
+ * (ctc_rowreg.hip) and width 16, where float32 has instances with the width as a constant, the
+ * half types take the any-width instance -- same results: every instance gives the same bits.
+ * ------------------------------------------------------------------------------------- */
+int pdt_ctc_prefix_search_elem(const void *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                               int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
+                               int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
+                               void *workspace, void *stream, int elem);
+
+/* ---------------------------------------------------------------------------------------
  * The same search for beams the kernels above cannot hold: width <= 128, every frame in one launch
  * (csrc/ctc_search_wide.hip: one workgroup of eight waves per utterance, the beam's state in LDS
  * between frames, the workgroup selection of the plain step kernel; workgroups never wait on one
- * another).  Arguments, outputs and status codes as pdt_ctc_prefix_search; narrower widths are
+ * another).  Arguments, element types (pdt_ctc_prefix_search_wide_elem), outputs and status codes as
+ * pdt_ctc_prefix_search; narrower widths are
  * accepted too and give the same beams (probabilities may differ in the last bits: merged masses
  * are summed in index order here).  A frame with fewer than `width` candidates leaves the rest of
  * the beam absent: probability -inf, length 0, a zero column of y.
@@ -275,6 +297,17 @@ int pdt_ctc_prefix_search_wide(const float *logits, int64_t T, int64_t N, int64_
                                int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
                                int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
                                void *workspace, void *stream);
+
+/* The same with logits of the element type `elem` (see pdt_ctc_prefix_search_elem). */
+int pdt_ctc_prefix_search_wide_elem(const void *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                                    int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
+                                    int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
+                                    void *workspace, void *stream, int elem);
+
+/* Host only, no device work: the forms the wide search takes for rows of V tokens and this width --
+ * plan2 = {1: a frame's row of probabilities in LDS, 0: in the workspace; 1: the next-token tables in
+ * LDS, 0: in the workspace}.  PDT_E_TOO_LONG where pdt_ctc_prefix_search_wide returns it for the shape. */
+int pdt_ctc_prefix_search_wide_plan(int64_t V, int64_t width, int32_t *plan2);
 
 /* ---------------------------------------------------------------------------------------
  * ctc_prefix_search_advance (reference _decoding.py:636-934): one CTC prefix-search step with
@@ -504,16 +537,17 @@ int pdt_random_walk_table(const float *table, int64_t tb_sr, int64_t R, int64_t 
                           void *stream);
 
 /* ---------------------------------------------------------------------------------------
- * ctc_greedy_search (reference _decoding.py:507-558).  logits (T, N, V) through element
+ * ctc_greedy_search (reference _decoding.py:507-558).  logits (T, N, V) float32 (float16 /
+ * bfloat16: the _elem entry points below, see pdt_ctc_prefix_search_elem) through element
  * strides; blank_idx already normalised to [0, V).  max_out (N,): sum of the per-frame maximum
  * log-probabilities (is_probs: product of the maxima, no normalisation) over frames below
  * in_lens; paths (T, N) int64 through strides: the first out_lens[n] entries of column n are
  * the collapsed tokens, the rest the raw per-frame arg-max (as the reference leaves them).
  *
  * sequence_log_probs on tensors (_decoding.py:1516-1551).  hyp viewed as (A, S, B) with S the
- * step axis, logits (A, S, B, V) contiguous; out (A, B) = sum over valid steps of
+ * step axis, logits (A, S, B, V) contiguous, of the same element types; out (A, B) float32 = sum over valid steps of
  * log_softmax(logits)[hyp]; tokens outside [0, V) and steps after the first eos are skipped.
- * Backward: grad_logits (same layout) from grad_out (A, B).
+ * Backward: grad_logits (same layout, the logits' element type) from grad_out (A, B) float32.
  * PDT_E_TOO_LONG: V >= 2^30 (all three; V is an int in the kernels), T beyond the LDS of the greedy
  * search (more than 20 480 frames), N, A, S, B or A * B >= 2^31.
  * ------------------------------------------------------------------------------------- */
@@ -522,13 +556,27 @@ int pdt_ctc_greedy_search(const float *logits, int64_t T, int64_t N, int64_t V, 
                           int is_probs, float *max_out, int64_t *paths, int64_t pa_st,
                           int64_t pa_sn, int64_t *out_lens, void *stream);
 
+/* (the three below: logits of the element type `elem`, see pdt_ctc_prefix_search_elem) */
+int pdt_ctc_greedy_search_elem(const void *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                               int64_t lg_sn, int64_t lg_sv, const int64_t *in_lens, int64_t blank_idx,
+                               int is_probs, float *max_out, int64_t *paths, int64_t pa_st,
+                               int64_t pa_sn, int64_t *out_lens, void *stream, int elem);
+
 int pdt_sequence_log_probs_forward(const float *logits, const int64_t *hyp, int64_t A, int64_t S,
                                    int64_t B, int64_t V, int has_eos, int64_t eos, float *out,
                                    void *stream);
 
+int pdt_sequence_log_probs_forward_elem(const void *logits, const int64_t *hyp, int64_t A, int64_t S,
+                                        int64_t B, int64_t V, int has_eos, int64_t eos, float *out,
+                                        void *stream, int elem);
+
 int pdt_sequence_log_probs_backward(const float *logits, const int64_t *hyp, int64_t A, int64_t S,
                                     int64_t B, int64_t V, int has_eos, int64_t eos,
                                     const float *grad_out, float *grad_logits, void *stream);
+
+int pdt_sequence_log_probs_backward_elem(const void *logits, const int64_t *hyp, int64_t A, int64_t S,
+                                         int64_t B, int64_t V, int has_eos, int64_t eos,
+                                         const float *grad_out, void *grad_logits, void *stream, int elem);
 
 /* ---------------------------------------------------------------------------------------
  * Feature augmentation / image warps (reference _img.py).  All tensors float32 and

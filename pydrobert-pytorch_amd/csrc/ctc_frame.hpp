@@ -47,7 +47,7 @@ __device__ unsigned g_utt_stats[8192 * 4];
 constexpr int kMaxWidth = 32;  // K + K' <= 64 tokens fit one per lane
 
 struct CtcArgs {
-  const float *logits;  // (T, N, V + 1), element strides below
+  const float *logits;  // (T, N, V + 1), element strides below (the searches' half-precision instances read it as their element type)
   int64_t lg_st, lg_sn, lg_sv;
   const int64_t *lens;  // (N,) or null
   int T, N, V, W, S;    // S = rows of y

@@ -30,7 +30,7 @@
 // The rows are read once: long ones (more than 16 chunks of 64 per lane) as NON-TEMPORAL loads, so that they
 // do not push one another through the L2 -- C5 (V = 5000) 9.1 -> 8.65 ms on the box that measured both;
 // C3's 16-chunk rows lost 1.7 % that way and keep plain loads.
-#define PDT_ROW_LOAD(p) (NR > 16 ? __builtin_nontemporal_load(p) : *(p))
+#define PDT_ROW_LOAD(p) (NR > 16 ? elem_load_nt(p) : elem_load(p))
 #ifndef PDT_ROWREG_GUESS_MARGIN  // (a variant build with a huge one sends every guessed row down the
 #define PDT_ROWREG_GUESS_MARGIN 0x1p-16f  // margin-failure path: profiles/tools/dump_rowreg.py compares)
 #endif
@@ -69,10 +69,14 @@ constexpr int rowreg_waves(int NR) {
 // turn; a workgroup is one utterance: three producers and the consumer.
 // WC > 0: the beam width as a compile-time constant (the default, 16, has instantiations of its own:
 // the consumer's tier choices and table strides fold away, as in ctc_search.hip).
-template <int NR, int NF, int P, int WC = -1>
+// E: the logits' element type (float32, float16, bfloat16): a half element is widened exactly at its load --
+// the producers' row loads, plain and non-temporal, and the consumer's scattered one (pdt_common.hpp:
+// elem_load) -- into the registers the float32 rows occupy, lane l holding the elements l + 64 i as before.
+template <int NR, int NF, int P, int WC = -1, typename E = float>
 __global__ void __launch_bounds__(256, rowreg_waves(NR))
 ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
   extern __shared__ __align__(16) unsigned char smem[];
+  const E *const logits = reinterpret_cast<const E *>(a.logits);
   const int lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int u = wave / (P + 1);
@@ -112,17 +116,17 @@ ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
     float r[NR], rt = 0.0f;
     auto row_of = [&](int t) {
       // (rows are contiguous here -- the launcher sends strided logits to the LDS form -- so a
-      // chunk is base + lane * 4 + an immediate)
+      // chunk is base + lane * sizeof(element) + an immediate)
       int lq = lane;
       asm volatile("" : "+v"(lq));
-      return a.logits + (int64_t)t * a.lg_st + n * a.lg_sn + lq;
+      return logits + (int64_t)t * a.lg_st + n * a.lg_sn + lq;
     };
     if (pr < Tn) {
-      const float *row = row_of(pr);
+      const E *row = row_of(pr);
 #pragma unroll
       for (int i = 0; i < NR; ++i)
-        if (i < NF || i < nt_) r[i] = row[i * PDT_WAVE];
-      if (lane <= rem_) rt = row[nt_ * PDT_WAVE];
+        if (i < NF || i < nt_) r[i] = elem_load(&row[i * PDT_WAVE]);
+      if (lane <= rem_) rt = elem_load(&row[nt_ * PDT_WAVE]);
     }
     float thr_off = PDT_INF;  // the guessed survivor threshold: logit offset from the mean per-lane maximum (none yet)
     int sl = pr % NS;
@@ -206,7 +210,7 @@ ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
       // per-lane sums over v = lane, lane + 64, ... in order, then the DPP reduction: the other
       // forms' arithmetic.  A chunk's register is free once its numerator is in the sum: the next
       // row of this wave moves in behind it (the last rows of an utterance re-read their own).
-      const float *nrow = row_of(t + P < Tn ? t + P : t);
+      const E *nrow = row_of(t + P < Tn ? t + P : t);
       float s = 0.0f;
       // (ONE version of the unrolled pass, the tame one: a branch around two copies -- or a branch per
       // pair -- makes every chunk's register, reloaded behind its use, a merge of two versions, and the
@@ -228,14 +232,14 @@ ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
       if (!tame) {
         // masked (-inf) or far-off elements: the general routine over the row read again (L2), the
         // same per-lane order of additions
-        const float *row = a.logits + (int64_t)t * a.lg_st + n * a.lg_sn;
+        const E *row = logits + (int64_t)t * a.lg_st + n * a.lg_sn;
         s = 0.0f;
-        for (int v = lp; v < nt * PDT_WAVE; v += PDT_WAVE) s += exp_nonpos(row[v] - mx);
+        for (int v = lp; v < nt * PDT_WAVE; v += PDT_WAVE) s += exp_nonpos(elem_load(&row[v]) - mx);
       }
       const float et = in_row ? exp_nonpos(rt - mx) : 0.0f;  // (lanes beyond the blank add +0: no change)
       s += et;
       const float eb = readlane_f(et, rem);
-      if (in_row) rt = nrow[nt * PDT_WAVE];
+      if (in_row) rt = elem_load(&nrow[nt * PDT_WAVE]);
       s = wave_sum_f(s);
       const float inv0 = __builtin_amdgcn_rcpf(s);
       const float inv = __builtin_fmaf(__builtin_fmaf(-s, inv0, 1.0f), inv0, inv0);
@@ -262,10 +266,10 @@ ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
       } else {
         // heavy ties / clustered values: chunked top-64 merge.  Rare, and a register file cannot be
         // indexed by a loop counter: the row is read again (L2)
-        const float *row = a.logits + (int64_t)t * a.lg_st + n * a.lg_sn;
+        const E *row = logits + (int64_t)t * a.lg_st + n * a.lg_sn;
         for (int v0 = 0; v0 < V; v0 += PDT_WAVE) {
           const int v = v0 + lp;
-          const float x = v < V ? row[v] : -PDT_INF;
+          const float x = v < V ? elem_load(&row[v]) : -PDT_INF;
           const bool pred = v < V && x >= tq;
           if (__ballot(pred))
             tk = wave_merge_top64(tk, pred ? pack_key(fkey_nonneg(exp_nonpos(x - mx)), (unsigned)v) : 0ull);
@@ -313,9 +317,9 @@ ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
   // (with the width a constant the first frame runs with W entries too, all but the first invalid --
   // ctc_search.hip, kFullFromStart; rows here have at least 128 tokens)
   int Kp = WC > 0 ? WC : 1;
-  const float *lg_n = a.logits + n * a.lg_sn;
+  const E *lg_n = logits + n * a.lg_sn;
   // the logit of every prefix's last token in the coming frame (lanes beyond the beam read token 0)
-  float xg = Tn > 0 ? lg_n[0] : 0.0f;
+  float xg = Tn > 0 ? elem_load(&lg_n[0]) : 0.0f;
   int sl = 0;
   for (int t = 0; t < Tn; ++t, sl = sl + 1 == NS ? 0 : sl + 1) {
     if (__hip_atomic_load(&ready[sl], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= t) {
@@ -354,7 +358,7 @@ ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
     }
     if (lane == 0) __hip_atomic_store(consumed, t + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (t + 1 < Tn)
-      xg = lg_n[(int64_t)(t + 1) * a.lg_st + (int64_t)min(max(bm.last, 0), V - 1) * a.lg_sv];
+      xg = elem_load(&lg_n[(int64_t)(t + 1) * a.lg_st + (int64_t)min(max(bm.last, 0), V - 1) * a.lg_sv]);
     if (((t + 1) & ((1 << a.ckpt_shift) - 1)) == 0) {  // checkpoint (see CtcArgs::ckpt)
       const int c = ((t + 1) >> a.ckpt_shift) - 1;
       if (lane < W)
@@ -401,6 +405,10 @@ ctc_rowreg_kernel(const CtcArgs a, const RowregLayout rl) {
 
 constexpr int kRowregMaxChunks = 256;
 
+// The float16 and bfloat16 instances are translation units of their own (ctc_rowreg_f16.hip, ctc_rowreg_bf16.hip:
+// this file again with PDT_ROWREG_ELEM set to the element type), so that the three sets compile side by side;
+// the plan and the launcher's entry are this unit's.
+#ifndef PDT_ROWREG_ELEM
 // rows of 320 .. 16 447 tokens, beams the one-kernel search holds; PDT_CTC_ROWREG=0 keeps the LDS
 // rows of ctc_search.hip (comparisons)
 bool ctc_rowreg_applies(int V, int W) {
@@ -432,46 +440,56 @@ void ctc_rowreg_plan(int V, int W, int32_t *plan5) {
   plan5[0] = rl.producers; plan5[1] = rl.nstage; plan5[2] = rl.utt_per_wg; plan5[3] = 3;
   plan5[4] = rowreg_chunks(V);
 }
+#endif  // PDT_ROWREG_ELEM
 
-template <int NR, int NF, int P, int WC = -1>
+template <int NR, int NF, int P, int WC = -1, typename E = float>
 static int launch_rowreg(const CtcArgs &a, const RowregLayout &rl, hipStream_t stream) {
   const size_t smem = (size_t)rl.utt_bytes * rl.utt_per_wg;
-  if (const int rc = set_lds(ctc_rowreg_kernel<NR, NF, P, WC>, smem)) return rc;
+  if (const int rc = set_lds(ctc_rowreg_kernel<NR, NF, P, WC, E>, smem)) return rc;
   const unsigned grid = (unsigned)((a.N + rl.utt_per_wg - 1) / rl.utt_per_wg);
-  hipLaunchKernelGGL((ctc_rowreg_kernel<NR, NF, P, WC>), dim3(grid), dim3(256), smem, stream, a, rl);
+  hipLaunchKernelGGL((ctc_rowreg_kernel<NR, NF, P, WC, E>), dim3(grid), dim3(256), smem, stream, a, rl);
   return (int)hipGetLastError();
 }
 
 // full token chunks (the chunk with the blank has a register of its own): instantiations in steps of
 // eight chunks up to 80 (four waves per SIMD and more), of 16 up to 128 (three), of 32 up to 256 (two,
 // then one: the whole register file of a SIMD holds one row)
-template <int P, int WC = -1>
+template <int P, int WC = -1, typename E = float>
 static int launch_rowreg_nr(const CtcArgs &a, const RowregLayout &rl, hipStream_t stream) {
   const int c = a.V / PDT_WAVE;
   if (c <= 80) {
     switch ((c + 7) / 8) {
-      case 1: return launch_rowreg<8, 0, P, WC>(a, rl, stream);
-      case 2: return launch_rowreg<16, 8, P, WC>(a, rl, stream);
-      case 3: return launch_rowreg<24, 16, P, WC>(a, rl, stream);
-      case 4: return launch_rowreg<32, 24, P, WC>(a, rl, stream);
-      case 5: return launch_rowreg<40, 32, P, WC>(a, rl, stream);
-      case 6: return launch_rowreg<48, 40, P, WC>(a, rl, stream);
-      case 7: return launch_rowreg<56, 48, P, WC>(a, rl, stream);
-      case 8: return launch_rowreg<64, 56, P, WC>(a, rl, stream);
-      case 9: return launch_rowreg<72, 64, P, WC>(a, rl, stream);
-      default: return launch_rowreg<80, 72, P, WC>(a, rl, stream);
+      case 1: return launch_rowreg<8, 0, P, WC, E>(a, rl, stream);
+      case 2: return launch_rowreg<16, 8, P, WC, E>(a, rl, stream);
+      case 3: return launch_rowreg<24, 16, P, WC, E>(a, rl, stream);
+      case 4: return launch_rowreg<32, 24, P, WC, E>(a, rl, stream);
+      case 5: return launch_rowreg<40, 32, P, WC, E>(a, rl, stream);
+      case 6: return launch_rowreg<48, 40, P, WC, E>(a, rl, stream);
+      case 7: return launch_rowreg<56, 48, P, WC, E>(a, rl, stream);
+      case 8: return launch_rowreg<64, 56, P, WC, E>(a, rl, stream);
+      case 9: return launch_rowreg<72, 64, P, WC, E>(a, rl, stream);
+      default: return launch_rowreg<80, 72, P, WC, E>(a, rl, stream);
     }
   }
-  if (c <= 96) return launch_rowreg<96, 80, P, WC>(a, rl, stream);
-  if (c <= 112) return launch_rowreg<112, 96, P, WC>(a, rl, stream);
-  if (c <= 128) return launch_rowreg<128, 112, P, WC>(a, rl, stream);
-  if (c <= 160) return launch_rowreg<160, 128, P, WC>(a, rl, stream);
-  if (c <= 192) return launch_rowreg<192, 160, P, WC>(a, rl, stream);
-  if (c <= 224) return launch_rowreg<224, 192, P, WC>(a, rl, stream);
-  return launch_rowreg<256, 224, P, WC>(a, rl, stream);
+  if (c <= 96) return launch_rowreg<96, 80, P, WC, E>(a, rl, stream);
+  if (c <= 112) return launch_rowreg<112, 96, P, WC, E>(a, rl, stream);
+  if (c <= 128) return launch_rowreg<128, 112, P, WC, E>(a, rl, stream);
+  if (c <= 160) return launch_rowreg<160, 128, P, WC, E>(a, rl, stream);
+  if (c <= 192) return launch_rowreg<192, 160, P, WC, E>(a, rl, stream);
+  if (c <= 224) return launch_rowreg<224, 192, P, WC, E>(a, rl, stream);
+  return launch_rowreg<256, 224, P, WC, E>(a, rl, stream);
 }
 
-int launch_ctc_rowreg(CtcArgs a, hipStream_t stream) {
+#ifdef PDT_ROWREG_ELEM
+// (half logits: the instances of any width -- the width-16 set is float32's)
+int PDT_ROWREG_ELEM_LAUNCH(const CtcArgs &a, const RowregLayout &rl, hipStream_t stream) {
+  return launch_rowreg_nr<3, -1, PDT_ROWREG_ELEM>(a, rl, stream);
+}
+#else
+int launch_ctc_rowreg_f16(const CtcArgs &a, const RowregLayout &rl, hipStream_t stream);
+int launch_ctc_rowreg_bf16(const CtcArgs &a, const RowregLayout &rl, hipStream_t stream);
+
+int launch_ctc_rowreg(CtcArgs a, hipStream_t stream, int elem) {
   const RowregLayout rl = plan_ctc_rowreg(a.V, a.W);
   // checkpoint spacing: the (C + 1) x W table of the output walk overlays the ring and the position table
   const size_t room = (size_t)rl.slot_bytes * rl.nstage + rl.pos_bytes;
@@ -479,8 +497,11 @@ int launch_ctc_rowreg(CtcArgs a, hipStream_t stream) {
   while (((size_t)(a.T >> sh) + 1) * a.W * sizeof(int2) > room) ++sh;
   a.ckpt_shift = sh;
   a.ckpt_count = (a.T >> sh) + 1;
+  if (elem == 2) return launch_ctc_rowreg_f16(a, rl, stream);
+  if (elem == 3) return launch_ctc_rowreg_bf16(a, rl, stream);
   if (a.W == 16) return launch_rowreg_nr<3, 16>(a, rl, stream);
   return launch_rowreg_nr<3>(a, rl, stream);
 }
+#endif  // PDT_ROWREG_ELEM
 
 }  // namespace pdt

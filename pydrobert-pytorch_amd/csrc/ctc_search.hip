@@ -59,7 +59,12 @@ namespace pdt {
 // PAIR (the constant-shape instance, V = 256, W = 16): the producer takes TWO frames per pass, frame t in
 // lanes 0-31 and frame t + 1 in lanes 32-63 (32 lanes x 8 chunks + the blank): reductions, the 32-key
 // sort, the list and the header are paid once per pair of rows -- see the producer below.
-template <int P, int NT = -1, bool INREG = (P == 1), bool GROW = false, int WC = -1, int VC = -1, bool PAIR = false>
+// E: the logits' element type -- float32, float16 or bfloat16 (pdt_ctc_prefix_search_elem).  A half element is
+// widened exactly at its load (pdt_common.hpp: elem_load), one element per lane as the float32 loads, so the
+// prefetch registers, the ring, the lists and every sum hold what the float32 kernel holds on the widened
+// tensor.  Every element type has every instance, the constant-shape ones included (measured: without them the
+// headline shape took 1.50 / 1.70 ms on float16 / bfloat16 rows, with them 1.07 / 1.18).
+template <int P, int NT = -1, bool INREG = (P == 1), bool GROW = false, int WC = -1, int VC = -1, bool PAIR = false, typename E = float>
 __global__ void __launch_bounds__(256, INREG ? 8 : 4)
 ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
   static_assert(!INREG || P == 1, "the register-resident row pass is a one-producer form");
@@ -70,6 +75,7 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
   static_assert(!GROW || !INREG, "rows in the workspace are a form of the generic row pass");
   static_assert(NT < 0 || INREG, "compile-time chunk counts belong to the register-resident row pass");
   extern __shared__ __align__(16) unsigned char smem[];
+  const E *const logits = reinterpret_cast<const E *>(a.logits);
   const int lane = lane_id();
   // (wave-uniform by construction; telling the compiler keeps the utterance index and every
   // address derived from it in scalar registers)
@@ -162,12 +168,12 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
       float thr = PDT_INF;  // logit offset of the guessed threshold from the row mean (none yet: one survivor, a miss)
       float pre[8], preb = -PDT_INF;  // (preb: the blank's logit in the first lane of a half, -inf elsewhere)
       // rows of the pass after this one: a running pointer; the row past the last frame is the last frame again
-      const float *nrow = a.logits + n * (VC + 1) + hl + (int64_t)min(half, Tn - 1) * a.lg_st;
+      const E *nrow = logits + n * (VC + 1) + hl + (int64_t)min(half, Tn - 1) * a.lg_st;
       if (Tn > 0) {
 #pragma unroll
-        for (int i = 0; i < 8; ++i) pre[i] = nrow[i * 32];
+        for (int i = 0; i < 8; ++i) pre[i] = elem_load(&nrow[i * 32]);
         if (lane_predicate<kFirstLanes>()) {
-          preb = nrow[VC];
+          preb = elem_load(&nrow[VC]);
           __hip_atomic_store(&cnt[half], (int)surv_at, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
       }
@@ -243,8 +249,8 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
           // (two frames on; at the odd tail the upper half takes the frame the lower half arrives at)
           nrow += (t + 3 < Tn || half == 0) ? 2 * a.lg_st : a.lg_st;
 #pragma unroll
-          for (int i = 0; i < 8; ++i) pre[i] = nrow[i * 32];
-          if (lane_predicate<kFirstLanes>()) preb = nrow[VC];
+          for (int i = 0; i < 8; ++i) pre[i] = elem_load(&nrow[i * 32]);
+          if (lane_predicate<kFirstLanes>()) preb = elem_load(&nrow[VC]);
         }
         const float s = shfl_f(half_sum_at31(sA) + half_sum_at31(sB), last_of_half);
         const float inv0 = __builtin_amdgcn_rcpf(s);
@@ -322,11 +328,11 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
     const int nt_ = NT >= 0 ? NT : V / PDT_WAVE, rem_ = V - nt_ * PDT_WAVE;  // full token chunks; lane of the blank
     const float inv_ntok = 1.0f / (float)(nt_ > 0 ? nt_ * PDT_WAVE : 1);
     if (pr < Tn) {
-      const float *row0 = a.logits + (int64_t)pr * a.lg_st + n * lg_sn + (int64_t)lane * lg_sv;
+      const E *row0 = logits + (int64_t)pr * a.lg_st + n * lg_sn + (int64_t)lane * lg_sv;
 #pragma unroll
       for (int i = 0; i < kPrefetch; ++i) {
         const int v = lane + i * PDT_WAVE;
-        pre[i] = v <= V ? row0[(int64_t)(i * PDT_WAVE) * lg_sv] : 0.0f;
+        pre[i] = v <= V ? elem_load(&row0[(int64_t)(i * PDT_WAVE) * lg_sv]) : 0.0f;
       }
     }
     int sl = pr % NS;  // t % NS, kept by add / compare: no division in the loop
@@ -442,14 +448,14 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
         if (t + P < Tn) {
           // (lane term first: the per-element offsets are then wave-uniform scalars, not eight
           // hoisted 64-bit vector products)
-          const float *nrow = a.logits + (int64_t)(t + P) * a.lg_st + n * lg_sn + (int64_t)lp * lg_sv;
+          const E *nrow = logits + (int64_t)(t + P) * a.lg_st + n * lg_sn + (int64_t)lp * lg_sv;
 #pragma unroll
           for (int i = 0; i < kPrefetch; ++i) {
             if (i > nt) break;
             if (i < nt) {
-              pre[i] = nrow[(int64_t)(i * PDT_WAVE) * lg_sv];
+              pre[i] = elem_load(&nrow[(int64_t)(i * PDT_WAVE) * lg_sv]);
             } else if (i == nt) {
-              if (in_row) pre[i] = nrow[(int64_t)(i * PDT_WAVE) * lg_sv];
+              if (in_row) pre[i] = elem_load(&nrow[(int64_t)(i * PDT_WAVE) * lg_sv]);
             }
           }
         }
@@ -464,7 +470,7 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
           }
         }
         {
-          const float *row = a.logits + (int64_t)t * a.lg_st + n * lg_sn;
+          const E *row = logits + (int64_t)t * a.lg_st + n * lg_sn;
           int v = lane + kPrefetch * PDT_WAVE;
           if constexpr (!INREG) {
             // long rows: kBatch loads in flight, then the rest in guarded groups of 8 (a load that
@@ -473,7 +479,7 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
             for (; v + (kBatch - 1) * PDT_WAVE <= V; v += kBatch * PDT_WAVE) {
               float x[kBatch];
 #pragma unroll
-              for (int i = 0; i < kBatch; ++i) x[i] = row[(int64_t)(v + i * PDT_WAVE) * lg_sv];
+              for (int i = 0; i < kBatch; ++i) x[i] = elem_load(&row[(int64_t)(v + i * PDT_WAVE) * lg_sv]);
 #pragma unroll
               for (int i = 0; i < kBatch; ++i) {
                 p[v + i * PDT_WAVE] = x[i];
@@ -484,7 +490,7 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
               float x[8];
 #pragma unroll
               for (int i = 0; i < 8; ++i)
-                x[i] = v + i * PDT_WAVE <= V ? row[(int64_t)(v + i * PDT_WAVE) * lg_sv] : -PDT_INF;
+                x[i] = v + i * PDT_WAVE <= V ? elem_load(&row[(int64_t)(v + i * PDT_WAVE) * lg_sv]) : -PDT_INF;
 #pragma unroll
               for (int i = 0; i < 8; ++i) {
                 if (v + i * PDT_WAVE <= V) p[v + i * PDT_WAVE] = x[i];
@@ -493,7 +499,7 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
             }
           }
           for (; v <= V; v += PDT_WAVE) {
-            const float x = row[(int64_t)v * lg_sv];
+            const float x = elem_load(&row[(int64_t)v * lg_sv]);
             p[v] = x;
             mx = fmaxf(mx, x);
           }
@@ -501,11 +507,11 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
         if (t + P < Tn) {
           // (lane term first: the per-element offsets are then wave-uniform scalars, not eight
           // hoisted 64-bit vector products)
-          const float *nrow = a.logits + (int64_t)(t + P) * a.lg_st + n * lg_sn + (int64_t)lane * lg_sv;
+          const E *nrow = logits + (int64_t)(t + P) * a.lg_st + n * lg_sn + (int64_t)lane * lg_sv;
 #pragma unroll
           for (int i = 0; i < kPrefetch; ++i) {
             const int v = lane + i * PDT_WAVE;
-            if (v <= V) pre[i] = nrow[(int64_t)(i * PDT_WAVE) * lg_sv];
+            if (v <= V) pre[i] = elem_load(&nrow[(int64_t)(i * PDT_WAVE) * lg_sv]);
           }
         }
         mx = wave_max_f(mx);
@@ -799,12 +805,12 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
 #endif
 }
 
-template <int P, int NT = -1, bool INREG = (P == 1), bool GROW = false, int WC = -1, int VC = -1, bool PAIR = false>
+template <int P, int NT = -1, bool INREG = (P == 1), bool GROW = false, int WC = -1, int VC = -1, bool PAIR = false, typename E = float>
 static int launch_ctc_search_p(const CtcArgs &a, const RingLayout &rl, hipStream_t stream) {
   const size_t smem = (size_t)rl.utt_bytes * rl.utt_per_wg;
-  if (const int rc = set_lds(ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR>, smem)) return rc;
+  if (const int rc = set_lds(ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR, E>, smem)) return rc;
   const unsigned grid = (unsigned)((a.N + rl.utt_per_wg - 1) / rl.utt_per_wg);
-  hipLaunchKernelGGL((ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR>), dim3(grid), dim3(64 * (P + 1) * rl.utt_per_wg), smem,
+  hipLaunchKernelGGL((ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR, E>), dim3(grid), dim3(64 * (P + 1) * rl.utt_per_wg), smem,
                      stream, a, rl);
   return (int)hipGetLastError();
 }
@@ -861,27 +867,35 @@ __host__ inline int plan_ctc_search(int V, int W, CtcPlan *plan, RingLayout *rl)
 // rows held in the producers' registers (ctc_rowreg.hip)
 bool ctc_rowreg_applies(int V, int W);
 void ctc_rowreg_plan(int V, int W, int32_t *plan5);
-int launch_ctc_rowreg(CtcArgs a, hipStream_t stream);
+int launch_ctc_rowreg(CtcArgs a, hipStream_t stream, int elem);
 
-int launch_ctc_search(const CtcArgs &a, const CtcPlan &plan, const RingLayout &rl, hipStream_t stream) {
-  if (plan.inreg == 2) return launch_ctc_search_p<3, -1, false, true>(a, rl, stream);
-  if (plan.producers == 3) return launch_ctc_search_p<3>(a, rl, stream);
+// one selection for every element type: the same shape takes the same instance
+template <typename E>
+static int launch_ctc_search_e(const CtcArgs &a, const CtcPlan &plan, const RingLayout &rl, hipStream_t stream) {
+  if (plan.inreg == 2) return launch_ctc_search_p<3, -1, false, true, -1, -1, false, E>(a, rl, stream);
+  if (plan.producers == 3) return launch_ctc_search_p<3, -1, false, false, -1, -1, false, E>(a, rl, stream);
 #ifndef PDT_NO_V256  // (diagnostic builds compare against the run-time shapes)
   {
     const RingLayout c = ring_layout(256, 16, PDT_RING_STAGES, PDT_UTT_PER_WG, 1);
     if (a.V == 256 && a.W == 16 && a.ckpt_shift == 5 && !a.exact_div && !a.no_lean_extra && a.lg_sv == 1 && a.lg_sn == 257 && c.nstage == rl.nstage && c.utt_per_wg == rl.utt_per_wg && c.utt_bytes == rl.utt_bytes &&
         c.slot_bytes == rl.slot_bytes) {
       // (two frames per producer pass: four ring slots, a pair of them per pass)
-      if (switches().ctc_pair != 0 && rl.nstage == 4) return launch_ctc_search_p<1, 4, true, false, 16, 256, true>(a, rl, stream);
-      return launch_ctc_search_p<1, 4, true, false, 16, 256>(a, rl, stream);
+      if (switches().ctc_pair != 0 && rl.nstage == 4) return launch_ctc_search_p<1, 4, true, false, 16, 256, true, E>(a, rl, stream);
+      return launch_ctc_search_p<1, 4, true, false, 16, 256, false, E>(a, rl, stream);
     }
   }
 #endif
 #ifndef PDT_NO_WIDTH16
-  if (a.V / PDT_WAVE == 4 && a.W == 16) return launch_ctc_search_p<1, 4, true, false, 16>(a, rl, stream);
+  if (a.V / PDT_WAVE == 4 && a.W == 16) return launch_ctc_search_p<1, 4, true, false, 16, -1, false, E>(a, rl, stream);
 #endif
-  if (a.V / PDT_WAVE == 4) return launch_ctc_search_p<1, 4>(a, rl, stream);
-  return launch_ctc_search_p<1>(a, rl, stream);
+  if (a.V / PDT_WAVE == 4) return launch_ctc_search_p<1, 4, true, false, -1, -1, false, E>(a, rl, stream);
+  return launch_ctc_search_p<1, -1, true, false, -1, -1, false, E>(a, rl, stream);
+}
+
+int launch_ctc_search(const CtcArgs &a, const CtcPlan &plan, const RingLayout &rl, hipStream_t stream, int elem = 0) {
+  if (elem == 2) return launch_ctc_search_e<f16_t>(a, plan, rl, stream);
+  if (elem == 3) return launch_ctc_search_e<bf16_t>(a, plan, rl, stream);
+  return launch_ctc_search_e<float>(a, plan, rl, stream);
 }
 
 }  // namespace pdt
@@ -918,18 +932,20 @@ int pdt_ctc_prefix_search_plan(int64_t V, int64_t width, int32_t *plan5) {
   return PDT_OK;
 }
 
-int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
-                          int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
-                          int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
-                          void *workspace, void *stream) {
+int pdt_ctc_prefix_search_elem(const void *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                               int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
+                               int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
+                               void *workspace, void *stream, int elem) {
   using namespace pdt;
   if (T < 0 || N < 0 || V < 1 || width < 1 || S < 0) return PDT_E_ARG;
+  if (const int rc = elem_status(elem)) return rc;
   if (N == 0) return PDT_OK;
   if (!y_lens || !y_probs || (T > 0 && (!logits || !workspace)) || (S > 0 && !y)) return PDT_E_ARG;
   if (width > kMaxWidth) return PDT_E_TOO_LONG;
   if (T * width >= (1ll << 31) || V >= (1 << 30) || N >= (1ll << 31) || T >= (1 << 24)) return PDT_E_TOO_LONG;
   CtcArgs a{};
-  a.logits = logits; a.lg_st = lg_st; a.lg_sn = lg_sn; a.lg_sv = lg_sv;
+  a.logits = static_cast<const float *>(logits);  // (elements of `elem`: the kernel instance reads them as its own type)
+  a.lg_st = lg_st; a.lg_sn = lg_sn; a.lg_sv = lg_sv;
   a.lens = lens;
   a.T = (int)T; a.N = (int)N; a.V = (int)V; a.W = (int)width; a.S = (int)S;
   a.y = y; a.y_lens = y_lens; a.y_probs = y_probs;
@@ -941,14 +957,22 @@ int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, 
   a.no_steady = switches().ctc_steady == 0 ? 1 : 0;  // (no part of the plan: both values take the same instance)
   a.no_twoframe = (switches().ctc_twoframe == 0 || a.no_steady) ? 1 : 0;  // (likewise)
   // (contiguous rows: the register form addresses a row as base + immediates)
-  if (ctc_rowreg_applies(a.V, a.W) && lg_sv == 1) return launch_ctc_rowreg(a, (hipStream_t)stream);
+  if (ctc_rowreg_applies(a.V, a.W) && lg_sv == 1) return launch_ctc_rowreg(a, (hipStream_t)stream, elem);
   CtcPlan plan;
   RingLayout rl;
   const int rc = plan_ctc_search(a.V, a.W, &plan, &rl);
   if (rc != PDT_OK) return rc;
   a.ckpt_shift = ckpt_shift_for((int)T, (int)width, rl);
   a.ckpt_count = (int)(T >> a.ckpt_shift) + 1;
-  return launch_ctc_search(a, plan, rl, (hipStream_t)stream);
+  return launch_ctc_search(a, plan, rl, (hipStream_t)stream, elem);
+}
+
+int pdt_ctc_prefix_search(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                          int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
+                          int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
+                          void *workspace, void *stream) {
+  return pdt_ctc_prefix_search_elem(logits, T, N, V, lg_st, lg_sn, lg_sv, lens, width, S, y, y_lens, y_probs,
+                                    workspace, stream, 0);
 }
 
 }  // extern "C"

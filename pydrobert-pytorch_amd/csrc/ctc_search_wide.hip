@@ -1,4 +1,5 @@
-// pdt_ctc_prefix_search_wide -- CTCPrefixSearch(width)(logits, lens) without a language model
+// pdt_ctc_prefix_search_wide[_elem] -- CTCPrefixSearch(width)(logits, lens) without a language model, logits
+// of float32, float16 or bfloat16
 // (reference _decoding.py:1064-1202) for beams of up to 128 prefixes, every frame in ONE launch: the
 // persistent form of ctc_advance_wide_kernel (advance_wide.hip).  One workgroup of eight waves per
 // utterance loops over that utterance's frames; workgroups never wait on one another (no ring, no
@@ -45,7 +46,7 @@ constexpr int kWideMaxWidth = 128;
 constexpr int kWideNxtLdsWidth = PDT_WIDE_NXT_LDS_WIDTH;  // widths up to this keep the next-token tables in LDS
 
 struct CtcWideArgs {
-  const float *logits; int64_t lg_st, lg_sn, lg_sv;  // (T, N, V + 1)
+  const void *logits; int64_t lg_st, lg_sn, lg_sv;   // (T, N, V + 1) of the kernel's element type
   const int64_t *lens;                               // (N,) or null
   int T, N, V, W, S;
   int64_t *y;       // (S, N, W)
@@ -87,7 +88,9 @@ __device__ unsigned long long g_wide_walks;
 // bit b of entry a's row: a is a prefix of b
 __device__ __forceinline__ bool wide_rel(const u64 *bits, int a, int b) { return (bits[2 * a + (b >> 6)] >> (b & 63)) & 1ull; }
 
-template <bool ROW_LDS>
+// E: the logits' element type (float32, float16, bfloat16), widened exactly where the frame's row is read
+// (pdt_common.hpp: elem_load); the row of float32 values in LDS or the workspace and all behind it are one code.
+template <bool ROW_LDS, typename E = float>
 __global__ void __launch_bounds__(kWideThreads) ctc_search_wide_kernel(const CtcWideArgs a, const int nxt_in_lds) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int tid = (int)threadIdx.x, lane = lane_id(), wave = tid >> 6;
@@ -126,10 +129,10 @@ __global__ void __launch_bounds__(kWideThreads) ctc_search_wide_kernel(const Ctc
 #pragma unroll 1
   for (int t = 0; t < Tn; ++t) {
     // ---- the frame's softmax (:1093), blank = index V ----
-    const float *lg = a.logits + (int64_t)t * a.lg_st + n * a.lg_sn;
+    const E *lg = static_cast<const E *>(a.logits) + (int64_t)t * a.lg_st + n * a.lg_sn;
     float mx = -PDT_INF;
     for (int v = tid; v <= V; v += kWideThreads) {
-      const float x = lg[(int64_t)v * a.lg_sv];
+      const float x = elem_load(&lg[(int64_t)v * a.lg_sv]);
       row[v] = x;
       mx = fmaxf(mx, x);
     }
@@ -309,10 +312,10 @@ __global__ void __launch_bounds__(kWideThreads) ctc_search_wide_kernel(const Ctc
   }
 }
 
-template <bool ROW_LDS>
+template <bool ROW_LDS, typename E = float>
 static int launch_ctc_search_wide_p(const CtcWideArgs &a, const CtcWideLds &l, hipStream_t stream) {
-  if (const int rc = set_lds(ctc_search_wide_kernel<ROW_LDS>, l.total)) return rc;
-  hipLaunchKernelGGL((ctc_search_wide_kernel<ROW_LDS>), dim3((unsigned)a.N), dim3(kWideThreads), l.total, stream, a,
+  if (const int rc = set_lds(ctc_search_wide_kernel<ROW_LDS, E>, l.total)) return rc;
+  hipLaunchKernelGGL((ctc_search_wide_kernel<ROW_LDS, E>), dim3((unsigned)a.N), dim3(kWideThreads), l.total, stream, a,
                      l.nxt_lds ? 1 : 0);
   return (int)hipGetLastError();
 }
@@ -333,12 +336,23 @@ int64_t pdt_ctc_prefix_search_wide_workspace_bytes(int64_t T, int64_t N, int64_t
   return pdt::wide_trie_bytes(T, N, width) + pdt::wide_nxt_bytes(N, width) + pdt::wide_align(N * pdt::wide_row_stride(V) * 4) + 256;
 }
 
-int pdt_ctc_prefix_search_wide(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
-                               int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
-                               int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
-                               void *workspace, void *stream) {
+int pdt_ctc_prefix_search_wide_plan(int64_t V, int64_t width, int32_t *plan2) {
+  if (V < 1 || width < 1 || !plan2) return PDT_E_ARG;
+  if (width > pdt::kWideMaxWidth || V >= (1 << 30) || width * (V + 1) >= (1ll << 31)) return PDT_E_TOO_LONG;
+  const pdt::CtcWideLds l = pdt::ctc_wide_lds((int)V, (int)width);
+  if (l.total > 160 * 1024) return PDT_E_TOO_LONG;
+  plan2[0] = l.row_lds ? 1 : 0;
+  plan2[1] = l.nxt_lds ? 1 : 0;
+  return PDT_OK;
+}
+
+int pdt_ctc_prefix_search_wide_elem(const void *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                                    int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
+                                    int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
+                                    void *workspace, void *stream, int elem) {
   using namespace pdt;
   if (T < 0 || N < 0 || V < 1 || width < 1 || S < 0) return PDT_E_ARG;
+  if (const int rc = elem_status(elem)) return rc;
   if (N == 0) return PDT_OK;
   if (!y_lens || !y_probs || (T > 0 && (!logits || !workspace)) || (S > 0 && !y)) return PDT_E_ARG;
   if (width > kWideMaxWidth) return PDT_E_TOO_LONG;
@@ -356,8 +370,22 @@ int pdt_ctc_prefix_search_wide(const float *logits, int64_t T, int64_t N, int64_
   a.nxt = carve_as<int>(ws + wide_trie_bytes(T, N, width));
   a.rows = carve_as<float>(ws + wide_trie_bytes(T, N, width) + wide_nxt_bytes(N, width));
   a.row_stride = wide_row_stride(V);
+  if (elem == 2)
+    return l.row_lds ? launch_ctc_search_wide_p<true, f16_t>(a, l, (hipStream_t)stream)
+                     : launch_ctc_search_wide_p<false, f16_t>(a, l, (hipStream_t)stream);
+  if (elem == 3)
+    return l.row_lds ? launch_ctc_search_wide_p<true, bf16_t>(a, l, (hipStream_t)stream)
+                     : launch_ctc_search_wide_p<false, bf16_t>(a, l, (hipStream_t)stream);
   if (l.row_lds) return launch_ctc_search_wide_p<true>(a, l, (hipStream_t)stream);
   return launch_ctc_search_wide_p<false>(a, l, (hipStream_t)stream);
+}
+
+int pdt_ctc_prefix_search_wide(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                               int64_t lg_sn, int64_t lg_sv, const int64_t *lens, int64_t width,
+                               int64_t S, int64_t *y, int64_t *y_lens, float *y_probs,
+                               void *workspace, void *stream) {
+  return pdt_ctc_prefix_search_wide_elem(logits, T, N, V, lg_st, lg_sn, lg_sv, lens, width, S, y, y_lens, y_probs,
+                                         workspace, stream, 0);
 }
 
 }  // extern "C"

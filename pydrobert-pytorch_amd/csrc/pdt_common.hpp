@@ -27,6 +27,42 @@ static inline int set_lds(Kernel *kern, size_t smem, size_t cap = 64 * 1024) {
 
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 
+// Element types of the logits-sized inputs (the `elem` codes of include/pdt_amd.h: 0 float32, 2 float16,
+// 3 bfloat16).  A half element becomes a float32 AT THE LOAD, exactly -- float16 by the hardware convert
+// (subnormals included: the float16 denormal mode is on), bfloat16 by a 16-bit shift -- and everything
+// behind the load is the float32 code.  Loads are one element per lane: which lane holds which element,
+// and with it the order of every sum, is the float32 kernels'.
+using f16_t = _Float16;
+struct bf16_t {
+  unsigned short bits;
+};
+__device__ __forceinline__ float elem_load(const float *p) { return *p; }
+__device__ __forceinline__ float elem_load(const f16_t *p) { return (float)*p; }
+__device__ __forceinline__ float elem_load(const bf16_t *p) { return __uint_as_float((unsigned)p->bits << 16); }
+// the same as non-temporal loads (rows read once: ctc_rowreg.hip)
+__device__ __forceinline__ float elem_load_nt(const float *p) { return __builtin_nontemporal_load(p); }
+__device__ __forceinline__ float elem_load_nt(const f16_t *p) { return (float)__builtin_nontemporal_load(p); }
+__device__ __forceinline__ float elem_load_nt(const bf16_t *p) {
+  return __uint_as_float((unsigned)__builtin_nontemporal_load(&p->bits) << 16);
+}
+// float32 -> element, round to nearest even (what Tensor.to(dtype) does; NaN: the quiet NaN it writes)
+__device__ __forceinline__ void elem_store(float *p, float x) { *p = x; }
+__device__ __forceinline__ void elem_store(f16_t *p, float x) {
+  // (the float32 value as it stands: left in sight, a product in front of the conversion is folded into
+  // v_fma_mixlo_f16 -- ONE rounding of the exact product, not the float32 result's -- contraction off or not;
+  // 17 of a million gradient elements differed from the float32 kernel's cast)
+  asm volatile("" : "+v"(x));
+  *p = (f16_t)x;
+}
+__device__ __forceinline__ void elem_store(bf16_t *p, float x) {
+  const unsigned u = __float_as_uint(x);
+  p->bits = x != x ? (unsigned short)0x7FC0u : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+// status of an `elem` argument: float64 has no kernel, anything else but the three above is no code
+static inline int elem_status(int elem) {
+  return elem == 0 || elem == 2 || elem == 3 ? PDT_OK : (elem == 1 ? PDT_E_UNSUPPORTED : PDT_E_ARG);
+}
+
 // value of lane-1 (lane 0 receives `first`).  One v_mov_b32_dpp wave_shr:1.
 __device__ __forceinline__ float shr1(float v, float first) {
   return __int_as_float(__builtin_amdgcn_update_dpp(

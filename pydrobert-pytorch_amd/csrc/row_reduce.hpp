@@ -11,21 +11,22 @@ namespace pdt {
 // the packed (value, lowest index) arg-max key and sum_v exp(x[v] - max).  Rows beyond 64 * NR
 // elements are streamed twice, eight loads in flight.  The arg-max compares values, not bit
 // patterns: -0 + 0 = +0 puts both zeros on one key, so that -0 and +0 tie and the lower index wins.
+// The element type E (float32, float16, bfloat16) ends at the load (pdt_common.hpp: elem_load).
 struct RowStats {
   float mx, sum;
   u64 best;
 };
-template <int NR>
-__device__ __forceinline__ void row_load(const float *x, const int64_t sv, const int V, float (&r)[NR]) {
+template <int NR, typename E>
+__device__ __forceinline__ void row_load(const E *x, const int64_t sv, const int V, float (&r)[NR]) {
   const int lane = lane_id();
 #pragma unroll
   for (int i = 0; i < NR; ++i) {
     const int v = lane + i * PDT_WAVE;
-    r[i] = (i * PDT_WAVE < V && v < V) ? x[(int64_t)v * sv] : -PDT_INF;
+    r[i] = (i * PDT_WAVE < V && v < V) ? elem_load(&x[(int64_t)v * sv]) : -PDT_INF;
   }
 }
-template <bool WANT_ARG, bool WANT_SUM, int NR>
-__device__ __forceinline__ RowStats row_stats(const float *x, const int64_t sv, const int V, float (&r)[NR]) {
+template <bool WANT_ARG, bool WANT_SUM, int NR, typename E>
+__device__ __forceinline__ RowStats row_stats(const E *x, const int64_t sv, const int V, float (&r)[NR]) {
   const int lane = lane_id();
   RowStats st;
   st.sum = 0.0f;
@@ -49,7 +50,7 @@ __device__ __forceinline__ RowStats row_stats(const float *x, const int64_t sv, 
     for (int v0 = 0; v0 < V; v0 += 8 * PDT_WAVE) {
       float t[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) t[i] = v0 + i * PDT_WAVE + lane < V ? x[(int64_t)(v0 + i * PDT_WAVE + lane) * sv] : -PDT_INF;
+      for (int i = 0; i < 8; ++i) t[i] = v0 + i * PDT_WAVE + lane < V ? elem_load(&x[(int64_t)(v0 + i * PDT_WAVE + lane) * sv]) : -PDT_INF;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
         mx = fmaxf(mx, t[i]);
@@ -80,7 +81,7 @@ __device__ __forceinline__ RowStats row_stats(const float *x, const int64_t sv, 
       for (int v0 = 0; v0 < V; v0 += 8 * PDT_WAVE) {
         float t[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) t[i] = v0 + i * PDT_WAVE + lane < V ? x[(int64_t)(v0 + i * PDT_WAVE + lane) * sv] : -PDT_INF;
+        for (int i = 0; i < 8; ++i) t[i] = v0 + i * PDT_WAVE + lane < V ? elem_load(&x[(int64_t)(v0 + i * PDT_WAVE + lane) * sv]) : -PDT_INF;
 #pragma unroll
         for (int i = 0; i < 8; ++i) s += expf(t[i] - st.mx);
       }

@@ -6,7 +6,10 @@
 //   pdt_sequence_log_probs_{forward,backward} -- sequence_log_probs on tensors
 //       (_decoding.py:1516-1551): log_softmax + gather + masked sum over the step axis, fused;
 //       the backward writes softmax-minus-onehot rows scaled by the upstream gradient.
-// Both are HBM-bound on the logits (4 * V bytes per frame) -- once every row is read with all its
+// The logits are float32, float16 or bfloat16 (the _elem entry points; pdt_common.hpp: elem_load): a half
+// element is widened exactly at its load and the arithmetic is the float32 kernel's, so the results are
+// those of the float32 entry point on the widened tensor, bit for bit, without that tensor being made.
+// Both are HBM-bound on the logits (sizeof(element) * V bytes per frame) -- once every row is read with all its
 // loads in flight and the rows of one sequence are spread over the waves of a workgroup: frames
 // are independent, only the reductions over them are ordered.  (Round 1 walked the frames of a
 // sequence with one wave, one 64-element load at a time, and sequence_log_probs re-derived the
@@ -16,8 +19,9 @@
 
 namespace pdt {
 
+template <typename E>
 struct GreedyArgs {
-  const float *logits; int64_t lg_st, lg_sn, lg_sv;  // (T, N, V) through element strides
+  const E *logits; int64_t lg_st, lg_sn, lg_sv;  // (T, N, V) through element strides
   const int64_t *in_lens;   // (N,) or null
   int T, N, V, blank, is_probs;
   float *max_out;           // (N,)
@@ -28,8 +32,8 @@ struct GreedyArgs {
 };
 
 // One workgroup per utterance; its waves take the frames t = w, w + NW, ...
-template <int NR>
-__global__ void __launch_bounds__(1024) ctc_greedy_kernel(const GreedyArgs a) {
+template <int NR, typename E = float>
+__global__ void __launch_bounds__(1024) ctc_greedy_kernel(const GreedyArgs<E> a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int lane = lane_id();
   const int wave = (int)(threadIdx.x >> 6), NW = a.nw;
@@ -39,7 +43,7 @@ __global__ void __launch_bounds__(1024) ctc_greedy_kernel(const GreedyArgs a) {
   const int T = a.T, V = a.V;
   const int in_len = a.in_lens ? (int)min((int64_t)T, max((int64_t)0, a.in_lens[n])) : T;
   for (int t = wave; t < T; t += NW) {
-    const float *x = a.logits + (int64_t)t * a.lg_st + n * a.lg_sn;
+    const E *x = a.logits + (int64_t)t * a.lg_st + n * a.lg_sn;
     float r[NR];
     // frames beyond the length contribute 0 (log) or 1 (prob), :540-543 -- but their arg-max is
     // still reported in the tail of `paths`
@@ -88,15 +92,16 @@ __global__ void __launch_bounds__(1024) ctc_greedy_kernel(const GreedyArgs a) {
 
 // ---- sequence_log_probs -------------------------------------------------------------------
 // hyp viewed as (A, S, B): A = dims before the step axis, S = steps, B = dims after it.
+template <typename E>
 struct SlpArgs {
-  const float *logits;      // hyp.shape + (V,), contiguous
+  const E *logits;          // hyp.shape + (V,), contiguous
   const int64_t *hyp;       // (A, S, B) contiguous
   int A, S, B, V;
   int has_eos;
   int64_t eos;
   float *out;               // (A, B)
   const float *grad_out;    // backward (A, B)
-  float *grad_logits;       // backward, same layout as logits
+  E *grad_logits;           // backward, same layout and element type as logits (rounded to nearest even)
   int nw;                   // waves per sequence
 };
 
@@ -105,8 +110,8 @@ struct SlpArgs {
 // ballots over 64 steps at a time.  Forward: per-wave partial sums in step order, combined in wave
 // order (deterministic).  Backward: each row is read once into registers and its gradient row
 // written once.
-template <bool BACKWARD, int NR>
-__global__ void __launch_bounds__(1024) slp_kernel(const SlpArgs a) {
+template <bool BACKWARD, int NR, typename E = float>
+__global__ void __launch_bounds__(1024) slp_kernel(const SlpArgs<E> a) {
   __shared__ int s_len;
   __shared__ float s_part[16];
   const int lane = lane_id();
@@ -149,26 +154,26 @@ __global__ void __launch_bounds__(1024) slp_kernel(const SlpArgs a) {
       const int64_t tok = __shfl(tok_mine, j);
       const int64_t row = ((int64_t)ai * S + s) * a.B + bi;
       const bool masked = tok < 0 || tok >= V || s >= len;
-      float *go = BACKWARD ? a.grad_logits + row * (int64_t)V : nullptr;
+      E *go = BACKWARD ? a.grad_logits + row * (int64_t)V : nullptr;
       if (masked) {
         if (BACKWARD)
-          for (int v = lane; v < V; v += PDT_WAVE) go[v] = 0.0f;
+          for (int v = lane; v < V; v += PDT_WAVE) elem_store(&go[v], 0.0f);
         continue;
       }
-      const float *x = a.logits + row * (int64_t)V;
+      const E *x = a.logits + row * (int64_t)V;
       float r[NR];
       const RowStats st = row_stats<false, true, NR>(x, 1, V, r);
       const float lse = st.mx + logf(st.sum);
       if (!BACKWARD) {
-        acc += (x[tok] - st.mx) - logf(st.sum);
+        acc += (elem_load(&x[tok]) - st.mx) - logf(st.sum);
       } else if (V <= NR * PDT_WAVE) {
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
           const int v = lane + i * PDT_WAVE;
-          if (i * PDT_WAVE < V && v < V) go[v] = g * ((v == tok ? 1.0f : 0.0f) - expf(r[i] - lse));
+          if (i * PDT_WAVE < V && v < V) elem_store(&go[v], g * ((v == tok ? 1.0f : 0.0f) - expf(r[i] - lse)));
         }
       } else {
-        for (int v = lane; v < V; v += PDT_WAVE) go[v] = g * ((v == tok ? 1.0f : 0.0f) - expf(x[v] - lse));
+        for (int v = lane; v < V; v += PDT_WAVE) elem_store(&go[v], g * ((v == tok ? 1.0f : 0.0f) - expf(elem_load(&x[v]) - lse)));
       }
     }
   }
@@ -189,67 +194,109 @@ static int seq_waves(int64_t steps) {
   return nw;
 }
 
+// ---- launchers, one instance set per element type ---------------------------------------------
+template <typename E>
+static int launch_greedy(const void *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st, int64_t lg_sn,
+                         int64_t lg_sv, const int64_t *in_lens, int64_t blank_idx, int is_probs,
+                         float *max_out, int64_t *paths, int64_t pa_st, int64_t pa_sn, int64_t *out_lens,
+                         size_t smem, void *stream) {
+  GreedyArgs<E> a{};
+  a.logits = static_cast<const E *>(logits); a.lg_st = lg_st; a.lg_sn = lg_sn; a.lg_sv = lg_sv;
+  a.in_lens = in_lens; a.T = (int)T; a.N = (int)N; a.V = (int)V; a.blank = (int)blank_idx;
+  a.is_probs = is_probs; a.max_out = max_out; a.paths = paths; a.pa_st = pa_st; a.pa_sn = pa_sn;
+  a.out_lens = out_lens; a.nw = seq_waves(T);
+  auto kern = V <= 8 * PDT_WAVE ? ctc_greedy_kernel<8, E> : ctc_greedy_kernel<16, E>;
+  if (const int rc = set_lds(kern, smem)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)N), dim3(64 * a.nw), smem, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+template <bool BACKWARD, typename E>
+static int launch_slp(const void *logits, const int64_t *hyp, int64_t A, int64_t S, int64_t B, int64_t V,
+                      int has_eos, int64_t eos, float *out, const float *grad_out, void *grad_logits,
+                      void *stream) {
+  SlpArgs<E> a{};
+  a.logits = static_cast<const E *>(logits); a.hyp = hyp; a.A = (int)A; a.S = (int)S; a.B = (int)B; a.V = (int)V;
+  a.has_eos = has_eos; a.eos = eos; a.out = out; a.grad_out = grad_out; a.grad_logits = static_cast<E *>(grad_logits);
+  a.nw = seq_waves(S);
+  auto kern = V <= 8 * PDT_WAVE ? slp_kernel<BACKWARD, 8, E> : slp_kernel<BACKWARD, 16, E>;
+  unsigned ny = 1u;
+  if (BACKWARD) {
+    ny = (unsigned)((S + (int64_t)a.nw * PDT_WAVE - 1) / ((int64_t)a.nw * PDT_WAVE));  // blocks of 64 nw steps
+    if (ny > 65535u) return PDT_E_TOO_LONG;
+  }
+  hipLaunchKernelGGL(kern, dim3((unsigned)(A * B), ny ? ny : 1u), dim3(64 * a.nw), 0, (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
 }  // namespace pdt
 
 extern "C" {
 
-int pdt_ctc_greedy_search(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
-                          int64_t lg_sn, int64_t lg_sv, const int64_t *in_lens, int64_t blank_idx,
-                          int is_probs, float *max_out, int64_t *paths, int64_t pa_st,
-                          int64_t pa_sn, int64_t *out_lens, void *stream) {
+int pdt_ctc_greedy_search_elem(const void *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                               int64_t lg_sn, int64_t lg_sv, const int64_t *in_lens, int64_t blank_idx,
+                               int is_probs, float *max_out, int64_t *paths, int64_t pa_st,
+                               int64_t pa_sn, int64_t *out_lens, void *stream, int elem) {
   using namespace pdt;
   if (T < 0 || N < 0 || V < 1 || blank_idx < 0 || blank_idx >= V) return PDT_E_ARG;
+  if (const int rc = elem_status(elem)) return rc;
   if (N == 0) return PDT_OK;
   if ((T > 0 && (!logits || !paths)) || !max_out || !out_lens) return PDT_E_ARG;
   const size_t smem = ((size_t)(T > 0 ? T : 1) * 8 + 15) & ~(size_t)15;  // arg-max + value per frame
   if (smem > 160 * 1024) return PDT_E_TOO_LONG;
   if (N > 0x7fffffffll) return PDT_E_TOO_LONG;
   if (V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel (row_reduce.hpp walks it in 64-token steps)
-  GreedyArgs a{};
-  a.logits = logits; a.lg_st = lg_st; a.lg_sn = lg_sn; a.lg_sv = lg_sv;
-  a.in_lens = in_lens; a.T = (int)T; a.N = (int)N; a.V = (int)V; a.blank = (int)blank_idx;
-  a.is_probs = is_probs; a.max_out = max_out; a.paths = paths; a.pa_st = pa_st; a.pa_sn = pa_sn;
-  a.out_lens = out_lens; a.nw = seq_waves(T);
-  auto kern = V <= 8 * PDT_WAVE ? ctc_greedy_kernel<8> : ctc_greedy_kernel<16>;
-  if (const int rc = set_lds(kern, smem)) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)N), dim3(64 * a.nw), smem, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  auto launch = elem == 0 ? launch_greedy<float> : (elem == 2 ? launch_greedy<f16_t> : launch_greedy<bf16_t>);
+  return launch(logits, T, N, V, lg_st, lg_sn, lg_sv, in_lens, blank_idx, is_probs, max_out, paths, pa_st, pa_sn,
+                out_lens, smem, stream);
+}
+
+int pdt_ctc_greedy_search(const float *logits, int64_t T, int64_t N, int64_t V, int64_t lg_st,
+                          int64_t lg_sn, int64_t lg_sv, const int64_t *in_lens, int64_t blank_idx,
+                          int is_probs, float *max_out, int64_t *paths, int64_t pa_st,
+                          int64_t pa_sn, int64_t *out_lens, void *stream) {
+  return pdt_ctc_greedy_search_elem(logits, T, N, V, lg_st, lg_sn, lg_sv, in_lens, blank_idx, is_probs, max_out,
+                                    paths, pa_st, pa_sn, out_lens, stream, 0);
+}
+
+int pdt_sequence_log_probs_forward_elem(const void *logits, const int64_t *hyp, int64_t A, int64_t S,
+                                        int64_t B, int64_t V, int has_eos, int64_t eos, float *out,
+                                        void *stream, int elem) {
+  using namespace pdt;
+  if (A < 0 || S < 0 || B < 0 || V < 1) return PDT_E_ARG;
+  if (const int rc = elem_status(elem)) return rc;
+  if (A * B == 0) return PDT_OK;
+  if ((S > 0 && (!logits || !hyp)) || !out) return PDT_E_ARG;
+  if (A * B >= (1ll << 31) || A >= (1ll << 31) || S >= (1ll << 31) || B >= (1ll << 31)) return PDT_E_TOO_LONG;
+  if (V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel
+  auto launch = elem == 0 ? launch_slp<false, float> : (elem == 2 ? launch_slp<false, f16_t> : launch_slp<false, bf16_t>);
+  return launch(logits, hyp, A, S, B, V, has_eos, eos, out, nullptr, nullptr, stream);
 }
 
 int pdt_sequence_log_probs_forward(const float *logits, const int64_t *hyp, int64_t A, int64_t S,
                                    int64_t B, int64_t V, int has_eos, int64_t eos, float *out,
                                    void *stream) {
+  return pdt_sequence_log_probs_forward_elem(logits, hyp, A, S, B, V, has_eos, eos, out, stream, 0);
+}
+
+int pdt_sequence_log_probs_backward_elem(const void *logits, const int64_t *hyp, int64_t A, int64_t S,
+                                         int64_t B, int64_t V, int has_eos, int64_t eos,
+                                         const float *grad_out, void *grad_logits, void *stream, int elem) {
   using namespace pdt;
   if (A < 0 || S < 0 || B < 0 || V < 1) return PDT_E_ARG;
-  if (A * B == 0) return PDT_OK;
-  if ((S > 0 && (!logits || !hyp)) || !out) return PDT_E_ARG;
+  if (const int rc = elem_status(elem)) return rc;
+  if (A * S * B == 0) return PDT_OK;
+  if (!logits || !hyp || !grad_out || !grad_logits) return PDT_E_ARG;
   if (A * B >= (1ll << 31) || A >= (1ll << 31) || S >= (1ll << 31) || B >= (1ll << 31)) return PDT_E_TOO_LONG;
   if (V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel
-  SlpArgs a{};
-  a.logits = logits; a.hyp = hyp; a.A = (int)A; a.S = (int)S; a.B = (int)B; a.V = (int)V;
-  a.has_eos = has_eos; a.eos = eos; a.out = out; a.nw = seq_waves(S);
-  auto kern = V <= 8 * PDT_WAVE ? slp_kernel<false, 8> : slp_kernel<false, 16>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(A * B)), dim3(64 * a.nw), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  auto launch = elem == 0 ? launch_slp<true, float> : (elem == 2 ? launch_slp<true, f16_t> : launch_slp<true, bf16_t>);
+  return launch(logits, hyp, A, S, B, V, has_eos, eos, nullptr, grad_out, grad_logits, stream);
 }
 
 int pdt_sequence_log_probs_backward(const float *logits, const int64_t *hyp, int64_t A, int64_t S,
                                     int64_t B, int64_t V, int has_eos, int64_t eos,
                                     const float *grad_out, float *grad_logits, void *stream) {
-  using namespace pdt;
-  if (A < 0 || S < 0 || B < 0 || V < 1) return PDT_E_ARG;
-  if (A * S * B == 0) return PDT_OK;
-  if (!logits || !hyp || !grad_out || !grad_logits) return PDT_E_ARG;
-  if (A * B >= (1ll << 31) || A >= (1ll << 31) || S >= (1ll << 31) || B >= (1ll << 31)) return PDT_E_TOO_LONG;
-  if (V >= (1 << 30)) return PDT_E_TOO_LONG;  // V is an int in the kernel
-  SlpArgs a{};
-  a.logits = logits; a.hyp = hyp; a.A = (int)A; a.S = (int)S; a.B = (int)B; a.V = (int)V;
-  a.has_eos = has_eos; a.eos = eos; a.grad_out = grad_out; a.grad_logits = grad_logits; a.nw = seq_waves(S);
-  auto kern = V <= 8 * PDT_WAVE ? slp_kernel<true, 8> : slp_kernel<true, 16>;
-  const unsigned ny = (unsigned)((S + (int64_t)a.nw * PDT_WAVE - 1) / ((int64_t)a.nw * PDT_WAVE));  // blocks of 64 nw steps
-  if (ny > 65535u) return PDT_E_TOO_LONG;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(A * B), ny ? ny : 1u), dim3(64 * a.nw), 0, (hipStream_t)stream, a);
-  return (int)hipGetLastError();
+  return pdt_sequence_log_probs_backward_elem(logits, hyp, A, S, B, V, has_eos, eos, grad_out, grad_logits, stream, 0);
 }
 
 }  // extern "C"

@@ -30,7 +30,10 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # ConcatSoftAttention score (pdt_concat_score, pdt_concat_score_backward, pdt_concat_score_workspace_bytes,
 # pdt_concat_score_plan) and the warps' position gradients with the spline evaluation's adjoint
 # (pdt_dense_image_warp_flow_backward[_f64], pdt_sparse_image_warp_position_backward[_f64],
-# pdt_spline_eval_adjoint, pdt_spline_eval_adjoint_plan).
+# pdt_spline_eval_adjoint, pdt_spline_eval_adjoint_plan) and the entry points that read float16 / bfloat16
+# logits as they are (pdt_ctc_prefix_search_elem, pdt_ctc_prefix_search_wide_elem, pdt_ctc_greedy_search_elem,
+# pdt_sequence_log_probs_forward_elem, pdt_sequence_log_probs_backward_elem: new names beside the float32 ones,
+# which keep their declarations) with the host-only pdt_ctc_prefix_search_wide_plan.
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -281,6 +284,23 @@ SIGNATURES = {
     "pdt_ctc_prefix_search_wide": (
         _INT,
         [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P],
+    ),
+    # logits of float32 / float16 / bfloat16 read as they are: the siblings' arguments + the element code
+    "pdt_ctc_prefix_search_elem": (
+        _INT,
+        [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _INT],
+    ),
+    "pdt_ctc_prefix_search_wide_elem": (
+        _INT,
+        [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _I64, _P, _P, _P, _P, _P, _INT],
+    ),
+    "pdt_ctc_prefix_search_wide_plan": (_INT, [_I64, _I64, _P]),
+    "pdt_ctc_greedy_search_elem": (
+        _INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _I64, _INT, _P, _P, _I64, _I64, _P, _P, _INT],
+    ),
+    "pdt_sequence_log_probs_forward_elem": (_INT, [_P, _P, _I64, _I64, _I64, _I64, _INT, _I64, _P, _P, _INT]),
+    "pdt_sequence_log_probs_backward_elem": (
+        _INT, [_P, _P, _I64, _I64, _I64, _I64, _INT, _I64, _P, _P, _P, _INT],
     ),
 }
 

@@ -18,7 +18,7 @@ from torch.library import custom_op
 
 from . import _cabi, argcheck, config, switches
 from ._lm import ExtractableSequentialLanguageModel, LookupLanguageModel, MixableSequentialLanguageModel
-from ._step import _ctc_step_with_lm_scores, _f32, _i64, ctc_prefix_search_advance
+from ._step import _ctc_step_with_lm_scores, _f32, _i64, _logits_elem, ctc_prefix_search_advance
 
 __all__ = ["BeamSearch", "CTCPrefixSearch", "ctc_prefix_search"]
 
@@ -43,7 +43,7 @@ def _ctc_prefix_search_op(
         raise RuntimeError("the one-kernel search holds at most {} prefixes".format(MAX_CTC_WIDTH))
     wide = width > MAX_CTC_WAVE_WIDTH
     dtype = logits.dtype
-    logits = _f32(logits)
+    logits, elem = _logits_elem(logits)  # (float16 / bfloat16: read as they are, no float32 copy)
     if lens is None:
         S = T
     elif lens.dim() != 1:
@@ -61,11 +61,15 @@ def _ctc_prefix_search_op(
         y_probs = torch.empty((N, width), device=device, dtype=torch.float)
         ws_bytes = L.pdt_ctc_prefix_search_wide_workspace_bytes if wide else L.pdt_ctc_prefix_search_workspace_bytes
         ws = torch.empty((int(ws_bytes(T, N, V, width)),), device=device, dtype=torch.uint8)
-        rc = (L.pdt_ctc_prefix_search_wide if wide else L.pdt_ctc_prefix_search)(
+        args = (
             _cabi.ptr(logits), T, N, V, logits.stride(0), logits.stride(1), logits.stride(2),
             _cabi.ptr(lens), int(width), S, _cabi.ptr(y), _cabi.ptr(y_lens), _cabi.ptr(y_probs),
             _cabi.ptr(ws), _cabi.stream_ptr(device),
         )  # fmt: skip
+        if elem:  # float16 / bfloat16: the entry point that takes the element type
+            rc = (L.pdt_ctc_prefix_search_wide_elem if wide else L.pdt_ctc_prefix_search_elem)(*args, elem)
+        else:
+            rc = (L.pdt_ctc_prefix_search_wide if wide else L.pdt_ctc_prefix_search)(*args)
     _cabi.check(rc, "pdt_ctc_prefix_search_wide" if wide else "pdt_ctc_prefix_search")
     return y, y_lens, y_probs.to(dtype)
 

@@ -8,7 +8,7 @@ import torch
 from torch.library import custom_op, register_autograd
 
 from . import _cabi, argcheck
-from ._step import _f32, _i64
+from ._step import _i64, _logits_elem
 
 __all__ = ["CTCGreedySearch", "SequenceLogProbabilities", "ctc_greedy_search", "sequence_log_probs"]
 
@@ -32,7 +32,7 @@ def _ctc_greedy_search_op(
         )
     blank_idx = (blank_idx + V) % V
     device = _cabi.require_hip(logits, in_lens)
-    x = _f32(logits)
+    x, elem = _logits_elem(logits)  # (float16 / bfloat16: read as they are, no float32 copy)
     if batch_first:
         N, T = x.shape[:2]
         st, sn = x.stride(1), x.stride(0)
@@ -45,10 +45,12 @@ def _ctc_greedy_search_op(
         paths = torch.empty((N, T) if batch_first else (T, N), device=device, dtype=torch.long)
         out_lens = torch.empty((N,), device=device, dtype=torch.long)
         pst, psn = (paths.stride(1), paths.stride(0)) if batch_first else (paths.stride(0), paths.stride(1))
-        rc = _cabi.lib().pdt_ctc_greedy_search(
+        args = (
             _cabi.ptr(x), T, N, V, st, sn, x.stride(2), _cabi.ptr(lens), blank_idx, int(is_probs),
             _cabi.ptr(max_), _cabi.ptr(paths), pst, psn, _cabi.ptr(out_lens), _cabi.stream_ptr(device),
         )  # fmt: skip
+        L = _cabi.lib()
+        rc = L.pdt_ctc_greedy_search_elem(*args, elem) if elem else L.pdt_ctc_greedy_search(*args)
     _cabi.check(rc, "pdt_ctc_greedy_search")
     return max_.to(logits.dtype), paths, out_lens
 
@@ -126,14 +128,17 @@ def _sequence_log_probs_op(
     if logits.shape[:-1] != hyp.shape:
         raise RuntimeError("logits must have shape hyp.shape + (num_classes,)")
     device = _cabi.require_hip(logits, hyp)
-    x = _f32(logits).contiguous()
+    x, elem = _logits_elem(logits)
+    x = x.contiguous()  # (in its own dtype)
     h = _i64(hyp).contiguous()
     with torch.cuda.device(device):
         out = torch.empty((A, B), device=device, dtype=torch.float)
-        rc = _cabi.lib().pdt_sequence_log_probs_forward(
+        args = (
             _cabi.ptr(x), _cabi.ptr(h), A, S, B, x.shape[-1], int(eos is not None),
             int(eos) if eos is not None else 0, _cabi.ptr(out), _cabi.stream_ptr(device),
         )  # fmt: skip
+        L = _cabi.lib()
+        rc = L.pdt_sequence_log_probs_forward_elem(*args, elem) if elem else L.pdt_sequence_log_probs_forward(*args)
     _cabi.check(rc, "pdt_sequence_log_probs_forward")
     shape = tuple(hyp.shape)
     return out.view(shape[:dim] + shape[dim + 1 :]).to(logits.dtype)
@@ -151,16 +156,19 @@ def _sequence_log_probs_backward_op(
 ) -> torch.Tensor:
     dim, A, S, B = _slp_dims(hyp, dim)
     device = logits.device
-    x = _f32(logits).contiguous()
+    x, elem = _logits_elem(logits)
+    x = x.contiguous()
     h = _i64(hyp).contiguous()
     g = grad_out.detach().float().contiguous()
     with torch.cuda.device(device):
-        grad = torch.empty_like(x)
-        rc = _cabi.lib().pdt_sequence_log_probs_backward(
+        grad = torch.empty_like(x)  # (the logits' dtype: the kernel rounds each element as .to(dtype) would)
+        args = (
             _cabi.ptr(x), _cabi.ptr(h), A, S, B, x.shape[-1], int(eos is not None),
             int(eos) if eos is not None else 0, _cabi.ptr(g), _cabi.ptr(grad),
             _cabi.stream_ptr(device),
         )  # fmt: skip
+        L = _cabi.lib()
+        rc = L.pdt_sequence_log_probs_backward_elem(*args, elem) if elem else L.pdt_sequence_log_probs_backward(*args)
     _cabi.check(rc, "pdt_sequence_log_probs_backward")
     return grad.view(logits.shape).to(logits.dtype)
 

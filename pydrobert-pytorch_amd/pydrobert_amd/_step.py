@@ -19,6 +19,19 @@ def _f32(t: torch.Tensor) -> torch.Tensor:
     return t if t.dtype == torch.float else t.float()
 
 
+# element codes of the ``_elem`` entry points the kernels read as they are (include/pdt_amd.h; _feats._DTYPES)
+_ELEM = {torch.float32: 0, torch.float16: 2, torch.bfloat16: 3}
+
+
+def _logits_elem(t: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """``(tensor, elem)`` for the logits of an ``_elem`` entry point: float32, float16 and bfloat16 are passed
+    as they are (detached, strides kept: the kernel widens a half element where it loads it); anything else --
+    float64 -- takes the narrowing copy of ``_f32``."""
+    if t.dtype in _ELEM:
+        return (t.detach() if t.requires_grad else t), _ELEM[t.dtype]
+    return _f32(t), 0
+
+
 def _i64(t: torch.Tensor) -> torch.Tensor:
     if t.requires_grad:
         t = t.detach()

@@ -163,7 +163,8 @@ int pdt_oc_expand(const uint32_t *bitmask, const int64_t *class_tokens, int64_t 
  * bitmask has H rows) instead of the expanded (H, N, C) targets:
  *   loss[h*N + n]  = mean over the completion set S of  -weight[t] * log_softmax(logits[h,n])[t]
  *   count[h*N + n] = |S| (targets equal to ignore_index are skipped), loss uses max(count, 1).
- * logits (H, N, V) float32 through element strides; weight (V,) or NULL.
+ * logits (H, N, V) float32 (float16 / bfloat16: the _elem entry points below) through element strides;
+ * weight (V,) or NULL.
  * Backward: grad_logits (H, N, V) contiguous from grad_loss (H, N).
  * status (optional) bit 0 is set when a target lies outside [0, V).
  * PDT_E_TOO_LONG: V >= 2^30, H, N or R above 2^31 - 1 (ints in the kernel), H * N >= 2^33.
@@ -179,6 +180,24 @@ int pdt_ocd_loss_backward(const float *logits, int64_t H, int64_t N, int64_t V, 
                           const int64_t *class_tokens, int64_t R, const float *weight,
                           int64_t ignore_index, const float *grad_loss, float *grad_logits,
                           void *stream);
+
+/* The same with logits -- and, in the backward, grad_logits -- of the element type `elem` (0 float32,
+ * 2 float16, 3 bfloat16; 1 returns PDT_E_UNSUPPORTED, any other value PDT_E_ARG: see
+ * pdt_ctc_prefix_search_elem), read and written as they are, without a float32 copy.  loss has the bits the
+ * float32 entry point gives on the widened logits, grad_logits those of its gradient rounded to the element
+ * type (nearest even).  weight, grad_loss, loss and count stay float32 / int32; rows need no alignment
+ * beyond the element's.  The element code and the pointers are checked before any device work. */
+int pdt_ocd_loss_forward_elem(const void *logits, int64_t H, int64_t N, int64_t V, int64_t lg_sh,
+                              int64_t lg_sn, int64_t lg_sv, const uint32_t *bitmask,
+                              const int64_t *class_tokens, int64_t R, const float *weight,
+                              int64_t ignore_index, float *loss, int32_t *count, int32_t *status,
+                              void *stream, int elem);
+
+int pdt_ocd_loss_backward_elem(const void *logits, int64_t H, int64_t N, int64_t V, int64_t lg_sh,
+                               int64_t lg_sn, int64_t lg_sv, const uint32_t *bitmask,
+                               const int64_t *class_tokens, int64_t R, const float *weight,
+                               int64_t ignore_index, const float *grad_loss, void *grad_logits,
+                               void *stream, int elem);
 
 /* ---------------------------------------------------------------------------------------
  * CTC prefix beam search with an N-GRAM language model in the loop, every frame from one launch

@@ -33,7 +33,8 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # pdt_spline_eval_adjoint, pdt_spline_eval_adjoint_plan) and the entry points that read float16 / bfloat16
 # logits as they are (pdt_ctc_prefix_search_elem, pdt_ctc_prefix_search_wide_elem, pdt_ctc_greedy_search_elem,
 # pdt_sequence_log_probs_forward_elem, pdt_sequence_log_probs_backward_elem: new names beside the float32 ones,
-# which keep their declarations) with the host-only pdt_ctc_prefix_search_wide_plan.
+# which keep their declarations) with the host-only pdt_ctc_prefix_search_wide_plan, and the same for the
+# hard-OCD loss (pdt_ocd_loss_forward_elem, pdt_ocd_loss_backward_elem).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -84,6 +85,12 @@ SIGNATURES = {
     ),
     "pdt_ocd_loss_backward": (
         _INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P],
+    ),
+    "pdt_ocd_loss_forward_elem": (
+        _INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _P, _INT],
+    ),
+    "pdt_ocd_loss_backward_elem": (
+        _INT, [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _I64, _P, _I64, _P, _P, _P, _INT],
     ),
     "pdt_ctc_prefix_search_advance": (
         _INT,

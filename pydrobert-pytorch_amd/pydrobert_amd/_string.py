@@ -16,6 +16,7 @@ import torch
 from torch.library import custom_op, register_autograd
 
 from . import _cabi, argcheck, config, switches
+from ._step import _logits_elem
 
 __all__ = [
     "EditDistance",
@@ -580,21 +581,21 @@ def _ocd_loss_rows_op(
         ref, hyp, eos, include_eos, batch_first, ins_cost, del_cost, sub_cost, True, warn,
         "pdt_oc_mask",
     )  # fmt: skip
-    x = logits.detach()
+    x, elem = _logits_elem(logits)  # (float16 / bfloat16: read as they are, strides kept, no float32 copy)
     if batch_first:
         x = x.transpose(0, 1)
-    if x.dtype != torch.float:
-        x = x.float()
     V = x.shape[2]
     w = None if weight is None else weight.detach().float().contiguous()
     with torch.cuda.device(device):
         loss = torch.empty((H, N), device=device, dtype=torch.float)
         count = torch.empty((H, N), device=device, dtype=torch.int32)
-        rc = _cabi.lib().pdt_ocd_loss_forward(
+        args = (
             _cabi.ptr(x), H, N, V, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(bitmask),
             _cabi.ptr(class_tokens), max(R, 1), _cabi.ptr(w), int(ignore_index), _cabi.ptr(loss),
             _cabi.ptr(count), scal.data_ptr() + 8, _cabi.stream_ptr(device),
         )  # fmt: skip
+        L = _cabi.lib()
+        rc = L.pdt_ocd_loss_forward_elem(*args, elem) if elem else L.pdt_ocd_loss_forward(*args)
     _cabi.check(rc, "pdt_ocd_loss_forward")
     if warn:
         _, flags, bad = (int(x) for x in scal.tolist())
@@ -629,25 +630,26 @@ def _ocd_loss_rows_backward_op(
 ) -> torch.Tensor:
     """d loss / d logits of ``ocd_loss_rows`` (csrc/ocd_loss.hip, BACKWARD)."""
     device = logits.device
-    x = logits.detach()
+    x, elem = _logits_elem(logits)
     if batch_first:
         x = x.transpose(0, 1)
-    if x.dtype != torch.float:
-        x = x.float()
     H, N, V = x.shape
     w = None if weight is None else weight.detach().float().contiguous()
     g = grad_loss.detach().float().contiguous()
     with torch.cuda.device(device):
-        grad = torch.empty((H, N, V), device=device, dtype=torch.float)
-        rc = _cabi.lib().pdt_ocd_loss_backward(
+        # (the dtype the kernel reads: a half gradient is rounded element by element as .to(dtype) would)
+        grad = torch.empty((H, N, V), device=device, dtype=x.dtype)
+        args = (
             _cabi.ptr(x), H, N, V, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(bitmask),
             _cabi.ptr(class_tokens), class_tokens.shape[1], _cabi.ptr(w), int(ignore_index),
             _cabi.ptr(g), _cabi.ptr(grad), _cabi.stream_ptr(device),
         )  # fmt: skip
+        L = _cabi.lib()
+        rc = L.pdt_ocd_loss_backward_elem(*args, elem) if elem else L.pdt_ocd_loss_backward(*args)
     _cabi.check(rc, "pdt_ocd_loss_backward")
     if batch_first:
         grad = grad.transpose(0, 1)
-    return grad.to(logits.dtype)
+    return grad.to(logits.dtype)  # (float64 logits only: every other dtype is the kernel's already)
 
 
 @_ocd_loss_rows_backward_op.register_fake

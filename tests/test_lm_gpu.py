@@ -112,6 +112,12 @@ def test_large_vocabulary_and_wide_types():
     act = lm(_t(hist.astype(np.int64)), None, -1)[0].cpu().numpy()
     brute = oracle.backoff_log_probs(dicts, V, sos, hist, 2)
     assert np.allclose(brute, act, atol=1e-4, equal_nan=True)
+    # ... and the same rows to the bit against the walk of the trie's own buffers
+    walk = oracle.trie_log_probs(
+        lm.logps.cpu().numpy(), lm.logbs.cpu().numpy(), lm.ids.cpu().numpy(),
+        lm.offsets.cpu().numpy(), V, sos, 3, hist, 2,
+    )  # fmt: skip
+    assert np.array_equal(walk, act, equal_nan=True), np.argwhere(walk != act)[:5].tolist()
 
 
 def test_state_dict_round_trip_on_device():

@@ -922,6 +922,35 @@ int pdt_attn_pool_backward(const int64_t *desc, int dtype, const void *score, co
                            const void *out, const void *lse, const void *grad_out, void *grad_score,
                            void *grad_value, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The same for operands of the element type `elem` (0 float32, 2 float16, 3 bfloat16; 1 returns
+ * PDT_E_UNSUPPORTED, any other value PDT_E_ARG, and the workspace query -1 for both: see
+ * pdt_ctc_prefix_search_elem).  query, key, value, score, out and grad_out are read, out and the gradients
+ * written, as elements of that type, without a float32 copy; rows need no alignment beyond the element's.
+ * Everything between is float32: lse is float32 (2, R) for every element type, and the plan -- tiles, spans,
+ * the choice of kernel, LDS and workspace bytes -- is that of the float32 call of the same descriptor.  out
+ * has the bits of the float32 entry point's on the widened operands rounded to the element type (nearest
+ * even), and the gradients those of its gradients on the widened operands and the widened out: each element
+ * is rounded once, where it is stored.  (The gradients are therefore exact for the rounded out that was saved,
+ * delta = rowsum(grad_out * out) included, not for the unrounded one.)  The element code and every argument
+ * are checked before any launch.  The entry points above keep refusing every dtype but 0 and 1. */
+int64_t pdt_attn_workspace_bytes_elem(const int64_t *desc, int elem, int kind);
+
+int pdt_attn_dot_elem(const int64_t *desc, int elem, const void *query, const void *key, const void *value,
+                      const void *mask, const double *scale, void *out, void *lse, void *workspace,
+                      int64_t workspace_bytes, void *stream);
+
+int pdt_attn_dot_backward_elem(const int64_t *desc, int elem, const void *query, const void *key, const void *value,
+                               const void *mask, const double *scale, const void *out, const void *lse,
+                               const void *grad_out, void *grad_query, void *grad_key, void *grad_value,
+                               void *workspace, int64_t workspace_bytes, void *stream);
+
+int pdt_attn_pool_elem(const int64_t *desc, int elem, const void *score, const void *value, const void *mask,
+                       void *out, void *lse, void *workspace, int64_t workspace_bytes, void *stream);
+
+int pdt_attn_pool_backward_elem(const int64_t *desc, int elem, const void *score, const void *value, const void *mask,
+                                const void *out, const void *lse, const void *grad_out, void *grad_score,
+                                void *grad_value, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * The additive ("concat") attention score (reference _attn.py:344-361) with the two halves of W
  * applied by the caller: e[r, t] = sum_h v[h] * tanh(a[r, h] + b[group(r), t, h]), formed without

@@ -1,8 +1,8 @@
 """Soft attention on MI355X (reference _attn.py:26-603): the five attention modules with the reference's
 signatures, parameters, initialisation order and error types.
 
-On a ROCm device (float32 / float64) the scores, the masked softmax and the weighted sum of values run as one
-HIP pass (``csrc/attn.hip``) that reads every key and value row once per group of rows sharing them, where the
+On a ROCm device (float32 / float64 / float16 / bfloat16) the scores, the masked softmax and the weighted sum of
+values run as one HIP pass (``csrc/attn.hip``) that reads every key and value row once per group of rows sharing them, where the
 reference materialises two products at the full broadcast shape.  Dot-product and generalized dot-product
 attention make one operator call, ``pydrobert_amd::dot_attention``: the generalized form transforms the query
 (``query @ weight``) instead of every key, and drops ``query . bias``, which is constant along ``dim`` and
@@ -10,7 +10,9 @@ cancels in the softmax.  ``ConcatSoftAttention`` applies the two halves of its `
 ``v . tanh`` in ``pydrobert_amd::concat_score`` (``csrc/concat_score.hip``), which builds no hidden-sized
 tensor; a subclass with its own ``score`` computes it with torch.  Either score then goes to
 ``pydrobert_amd::attention_pool`` for the masked softmax and the weighted sum.
-CPU tensors and other dtypes run the reference's formulas in torch.
+float16 / bfloat16 operands are read and written as they are (the ``_elem`` entry points: no float32 copy of any
+operand), computed in float32 and rounded once where a result is stored; ``lse`` is float32 for them.
+CPU tensors, other dtypes and operands of mixed dtypes run the reference's formulas in torch.
 
 Deviation: a masked frame contributes exactly 0 on the HIP path, where the reference multiplies it by 0 (a
 non-finite key or value in a masked frame gives NaN there and not here).
@@ -102,13 +104,13 @@ def _softmax_pool(e: torch.Tensor, value: torch.Tensor, mask: Optional[torch.Ten
 
 def _hip_route(e_shape: List[int], value: torch.Tensor, mask: Optional[torch.Tensor], dim: int,
                tensors: List[torch.Tensor], width: int) -> bool:  # fmt: skip
-    """True when the kernels compute what the reference's formula does: ROCm float32 / float64 tensors of one
-    dtype, a non-negative ``dim`` (with a negative one the reference's softmax and sum see different axes), a
-    bool mask that adds no dimension, a softmax axis as long as the summed one and at most eight row dims;
+    """True when the kernels compute what the reference's formula does: ROCm float32 / float64 / float16 /
+    bfloat16 tensors of one dtype, a non-negative ``dim`` (with a negative one the reference's softmax and sum see
+    different axes), a bool mask that adds no dimension, a softmax axis as long as the summed one and at most eight row dims;
     and one row of the tiles the kernels keep in LDS (``width`` features: D + Dv, or Dv for a given score)
-    fits their 56 KiB."""
+    fits their 56 KiB (the half types' tiles are float32)."""
     dt = tensors[0].dtype
-    if dt != torch.float32 and dt != torch.float64:
+    if dt != torch.float32 and dt != torch.float64 and dt != torch.float16 and dt != torch.bfloat16:
         return False
     if width * (8 if dt == torch.float64 else 4) > 57344:  # (kAttnLdsBytes)
         return False
@@ -137,15 +139,40 @@ def _hip_route(e_shape: List[int], value: torch.Tensor, mask: Optional[torch.Ten
 # operators
 
 
-def _dtype_code(x: torch.Tensor, *others, mask=None) -> int:
-    if x.dtype not in (torch.float32, torch.float64):
-        raise TypeError("the attention kernels take float32 or float64 tensors, got {}".format(x.dtype))
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def _dtype_code(x: torch.Tensor, *others, mask=None, half=False) -> int:
+    """The kernels' code of the operands' one dtype: 0 float32, 1 float64 and, with ``half`` (the attention
+    operators, whose ``_elem`` entry points take them), 2 float16, 3 bfloat16."""
+    if x.dtype not in (torch.float32, torch.float64) + (_HALF if half else ()):
+        raise TypeError("the attention kernels take {} tensors, got {}".format(
+            "float32, float64, float16 or bfloat16" if half else "float32 or float64", x.dtype))  # fmt: skip
     for t in others:
         if t.dtype != x.dtype:
             raise TypeError("attention operands of different dtypes: {} and {}".format(x.dtype, t.dtype))
     if mask is not None and mask.dtype != torch.bool:
         raise RuntimeError("the attention mask must be a bool tensor, got {}".format(mask.dtype))
-    return 0 if x.dtype == torch.float32 else 1
+    return {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3}[x.dtype]
+
+
+def _entry(name: str, dt: int):
+    """The entry point of an attention call: float16 / bfloat16 (codes 2, 3) go to the ``_elem`` sibling."""
+    return getattr(_cabi.lib(), name + "_elem" if dt >= 2 else name)
+
+
+def _lse_dtype(dtype: torch.dtype) -> torch.dtype:
+    return torch.float32 if dtype in _HALF else dtype
+
+
+def _sum_to(g: torch.Tensor, shape) -> torch.Tensor:
+    """``g.sum_to_size(shape)``: what broadcast an input had beyond the group.  A half gradient that is reduced
+    is summed in float32 and rounded once; one of the input's shape is returned as it is."""
+    if list(g.shape) == list(shape):
+        return g
+    if g.dtype in _HALF:
+        return g.float().sum_to_size(shape).to(g.dtype)
+    return g.sum_to_size(shape)
 
 
 def _full_shape(e_shape, value, mask):
@@ -224,10 +251,22 @@ def _contig_strides(shape: List[int]) -> List[int]:
 
 
 def _workspace(plan: _Plan, dt: int, kind: int, device) -> torch.Tensor:
-    nbytes = _cabi.lib().pdt_attn_workspace_bytes(plan.desc.data_ptr(), dt, kind)
+    nbytes = _entry("pdt_attn_workspace_bytes", dt)(plan.desc.data_ptr(), dt, kind)
     if nbytes < 0:
         raise RuntimeError("pdt_attn_workspace_bytes: invalid descriptor")
     return torch.empty((max(1, nbytes),), device=device, dtype=torch.uint8)
+
+
+def _saved(out: torch.Tensor, lse: torch.Tensor, plan: _Plan, dtype: torch.dtype):
+    """The forward's results as the backward kernels read them: ``out`` contiguous at the plan's shape in the
+    operands' dtype, ``lse`` (2, rows) in float32 for half operands (a wrong size would be read out of bounds)."""
+    if list(out.shape) != plan.out_shape or out.dtype != dtype:
+        raise RuntimeError("attention backward: out must be the forward's output, {} of {}; got {} of {}".format(
+            plan.out_shape, dtype, list(out.shape), out.dtype))  # fmt: skip
+    if list(lse.shape) != [2, plan.R] or lse.dtype != _lse_dtype(dtype):
+        raise RuntimeError("attention backward: lse must be the forward's, {} of {}; got {} of {}".format(
+            [2, plan.R], _lse_dtype(dtype), list(lse.shape), lse.dtype))  # fmt: skip
+    return out.detach().contiguous(), lse.detach().contiguous()
 
 
 def _dot_geometry(query, key, value, mask, dim):
@@ -258,10 +297,10 @@ def _dot_attention_op(
     that the backward reads, in the kernel's row order (kept apart: their sum would round away the second next
     to a large |score|)."""
     device = _cabi.require_hip(query, key, value, mask)
-    dt = _dtype_code(query, key, value, mask=mask)
+    dt = _dtype_code(query, key, value, mask=mask, half=True)
     plan, ops = _dot_plan(query, key, value, mask, dim)
     out = torch.empty(plan.out_shape, device=device, dtype=query.dtype)
-    lse = torch.empty((2, plan.R), device=device, dtype=query.dtype)
+    lse = torch.empty((2, plan.R), device=device, dtype=_lse_dtype(query.dtype))
     if plan.R == 0:
         return out, lse
     if plan.T == 0:
@@ -269,7 +308,7 @@ def _dot_attention_op(
     ws = _workspace(plan, dt, _KIND_DOT, device)
     scale_c = _cabi.ctypes.c_double(scale)
     with _cabi.on_device(device):
-        rc = _cabi.lib().pdt_attn_dot(
+        rc = _entry("pdt_attn_dot", dt)(
             plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[1].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]),
             _cabi.ctypes.addressof(scale_c), out.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws.numel(),
             _cabi.stream_ptr(device),
@@ -282,7 +321,7 @@ def _dot_attention_op(
 def _(query, key, value, mask, dim, scale):
     _, S = _dot_geometry(query, key, value, mask, dim)
     out_shape = S[:dim] + S[dim + 1:] + [value.shape[-1]]
-    return query.new_empty(out_shape), query.new_empty((2, _prod(out_shape[:-1])))
+    return query.new_empty(out_shape), query.new_empty((2, _prod(out_shape[:-1])), dtype=_lse_dtype(query.dtype))
 
 
 @custom_op("pydrobert_amd::dot_attention_backward", mutates_args=())
@@ -293,27 +332,30 @@ def _dot_attention_backward_op(
     """(grad_query, grad_key, grad_value) in the inputs' shapes.  The kernels sum grad_key / grad_value over
     the group; what other broadcast an input had is summed here."""
     device = _cabi.require_hip(grad_out, query, key, value, mask, out, lse)
-    dt = _dtype_code(query, key, value, mask=mask)
+    dt = _dtype_code(query, key, value, mask=mask, half=True)
     plan, ops = _dot_plan(query, key, value, mask, dim)
     D, Dv = query.shape[-1], value.shape[-1]
     if plan.R == 0 or plan.T == 0:
         return torch.zeros_like(query), torch.zeros_like(key), torch.zeros_like(value)
     g = grad_out.detach().to(query.dtype).contiguous()
+    if list(g.shape) != plan.out_shape:
+        raise RuntimeError("attention backward: grad_out of shape {}, out has {}".format(list(g.shape), plan.out_shape))
+    out_c, lse_c = _saved(out, lse, plan, query.dtype)
     gq = torch.empty(plan.out_shape[:-1] + [D], device=device, dtype=query.dtype)
     gk = torch.empty(plan.shared_shape + [D], device=device, dtype=query.dtype)
     gv = torch.empty(plan.shared_shape + [Dv], device=device, dtype=query.dtype)
     ws = _workspace(plan, dt, _KIND_DOT_BWD, device)
     scale_c = _cabi.ctypes.c_double(scale)
     with _cabi.on_device(device):
-        rc = _cabi.lib().pdt_attn_dot_backward(
+        rc = _entry("pdt_attn_dot_backward", dt)(
             plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[1].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]),
-            _cabi.ctypes.addressof(scale_c), out.data_ptr(), lse.data_ptr(), g.data_ptr(), gq.data_ptr(),
+            _cabi.ctypes.addressof(scale_c), out_c.data_ptr(), lse_c.data_ptr(), g.data_ptr(), gq.data_ptr(),
             gk.data_ptr(), gv.data_ptr(), ws.data_ptr(), ws.numel(), _cabi.stream_ptr(device),
         )  # fmt: skip
     _cabi.check(rc, "pdt_attn_dot_backward")
     q1_shape = list(query.unsqueeze(dim).shape)
-    gq = gq.unsqueeze(dim).sum_to_size(q1_shape).squeeze(dim)
-    return gq.reshape(query.shape), gk.sum_to_size(key.shape), gv.sum_to_size(value.shape)
+    gq = _sum_to(gq.unsqueeze(dim), q1_shape).squeeze(dim)
+    return gq.reshape(query.shape), _sum_to(gk, key.shape), _sum_to(gv, value.shape)
 
 
 @_dot_attention_backward_op.register_fake
@@ -341,17 +383,17 @@ def _attention_pool_op(
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     """(out, lse): the masked softmax of ``score`` over ``dim`` and the weighted sum of ``value``."""
     device = _cabi.require_hip(score, value, mask)
-    dt = _dtype_code(score, value, mask=mask)
+    dt = _dtype_code(score, value, mask=mask, half=True)
     plan, ops = _pool_plan(score, value, mask, dim)
     out = torch.empty(plan.out_shape, device=device, dtype=score.dtype)
-    lse = torch.empty((2, plan.R), device=device, dtype=score.dtype)
+    lse = torch.empty((2, plan.R), device=device, dtype=_lse_dtype(score.dtype))
     if plan.R == 0:
         return out, lse
     if plan.T == 0:
         return out.zero_(), lse.fill_(-float("inf"))
     ws = _workspace(plan, dt, _KIND_POOL, device)
     with _cabi.on_device(device):
-        rc = _cabi.lib().pdt_attn_pool(
+        rc = _entry("pdt_attn_pool", dt)(
             plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]), out.data_ptr(),
             lse.data_ptr(), ws.data_ptr(), ws.numel(), _cabi.stream_ptr(device),
         )  # fmt: skip
@@ -363,7 +405,7 @@ def _attention_pool_op(
 def _(score, value, mask, dim):
     S = _pool_geometry(score, value, mask, dim)
     out_shape = S[:dim] + S[dim + 1:] + [value.shape[-1]]
-    return score.new_empty(out_shape), score.new_empty((2, _prod(out_shape[:-1])))
+    return score.new_empty(out_shape), score.new_empty((2, _prod(out_shape[:-1])), dtype=_lse_dtype(score.dtype))
 
 
 @custom_op("pydrobert_amd::attention_pool_backward", mutates_args=())
@@ -373,22 +415,25 @@ def _attention_pool_backward_op(
 ) -> Tuple[torch.Tensor, torch.Tensor]:  # fmt: skip
     """(grad_score, grad_value) in the inputs' shapes."""
     device = _cabi.require_hip(grad_out, score, value, mask, out, lse)
-    dt = _dtype_code(score, value, mask=mask)
+    dt = _dtype_code(score, value, mask=mask, half=True)
     plan, ops = _pool_plan(score, value, mask, dim)
     if plan.R == 0 or plan.T == 0:
         return torch.zeros_like(score), torch.zeros_like(value)
     g = grad_out.detach().to(score.dtype).contiguous()
+    if list(g.shape) != plan.out_shape:
+        raise RuntimeError("attention backward: grad_out of shape {}, out has {}".format(list(g.shape), plan.out_shape))
+    out_c, lse_c = _saved(out, lse, plan, score.dtype)
     ge = torch.empty(plan.S, device=device, dtype=score.dtype)
     gv = torch.empty(plan.shared_shape + [value.shape[-1]], device=device, dtype=score.dtype)
     ws = _workspace(plan, dt, _KIND_POOL_BWD, device)
     with _cabi.on_device(device):
-        rc = _cabi.lib().pdt_attn_pool_backward(
-            plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]), out.data_ptr(),
-            lse.data_ptr(), g.data_ptr(), ge.data_ptr(), gv.data_ptr(), ws.data_ptr(), ws.numel(),
+        rc = _entry("pdt_attn_pool_backward", dt)(
+            plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]), out_c.data_ptr(),
+            lse_c.data_ptr(), g.data_ptr(), ge.data_ptr(), gv.data_ptr(), ws.data_ptr(), ws.numel(),
             _cabi.stream_ptr(device),
         )  # fmt: skip
     _cabi.check(rc, "pdt_attn_pool_backward")
-    return ge.sum_to_size(score.shape), gv.sum_to_size(value.shape)
+    return _sum_to(ge, score.shape), _sum_to(gv, value.shape)
 
 
 @_attention_pool_backward_op.register_fake

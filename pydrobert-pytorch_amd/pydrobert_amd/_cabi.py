@@ -34,7 +34,9 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # logits as they are (pdt_ctc_prefix_search_elem, pdt_ctc_prefix_search_wide_elem, pdt_ctc_greedy_search_elem,
 # pdt_sequence_log_probs_forward_elem, pdt_sequence_log_probs_backward_elem: new names beside the float32 ones,
 # which keep their declarations) with the host-only pdt_ctc_prefix_search_wide_plan, and the same for the
-# hard-OCD loss (pdt_ocd_loss_forward_elem, pdt_ocd_loss_backward_elem).
+# hard-OCD loss (pdt_ocd_loss_forward_elem, pdt_ocd_loss_backward_elem) and the attention entry points
+# (pdt_attn_workspace_bytes_elem, pdt_attn_dot_elem, pdt_attn_dot_backward_elem, pdt_attn_pool_elem,
+# pdt_attn_pool_backward_elem: the five without the suffix keep refusing every dtype code but 0 and 1).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -243,6 +245,13 @@ SIGNATURES = {
     ),
     "pdt_attn_pool": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_attn_pool_backward": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_attn_workspace_bytes_elem": (_I64, [_P, _INT, _INT]),
+    "pdt_attn_dot_elem": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_attn_dot_backward_elem": (
+        _INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
+    ),
+    "pdt_attn_pool_elem": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_attn_pool_backward_elem": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_concat_score_workspace_bytes": (_I64, [_P, _INT, _INT]),
     "pdt_concat_score_plan": (_INT, [_P, _INT, _P]),
     "pdt_concat_score": (_INT, [_P, _INT, _P, _P, _P, _P, _P]),

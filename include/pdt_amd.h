@@ -714,6 +714,45 @@ int pdt_spec_augment_apply_backward(const float *grad_out, int64_t N, int64_t T,
                                     const int64_t *f_0, const int64_t *f_len, int64_t MF,
                                     float *grad_feats, void *stream);
 
+/* The three application entry points on features kept in float16 / bfloat16, read and written as they are
+ * (new names; the declarations above are unchanged).  elem: 0 float32 -- the very launch of the entry point
+ * without the suffix --, 2 float16, 3 bfloat16; 1 (float64) is PDT_E_UNSUPPORTED, anything else PDT_E_ARG,
+ * judged with every pointer before any device work.  feats / out / grad_out / grad_feats are of that type,
+ * strides in elements; grids, warp parameters and masks stay float32 / int64.  The arithmetic is float32: a
+ * call is the float32 call on the exactly widened features, each result rounded once, to nearest even, where
+ * it is stored; a masked element is +0 whatever lies under the mask.
+ *   pdt_spec_augment_apply_form: host only, no device work -- the kernel the launchers take (they decide
+ *   through this function): 0 the general kernel, 1 the rows kernel (no frequency grid, F % 4 == 0, F <= 256,
+ *   f_sf == 1, f_st and f_sn multiples of 4 elements, in_addr and out_addr multiples of 4 element sizes; the
+ *   adjoint (backward = 1) takes its tensors as contiguous whatever strides are passed and adds 12 T + 1296
+ *   <= 65536 bytes of LDS).  No form moves eight elements per lane: 2 is never returned.  Negative: PDT_E_*
+ *   (the element code, negative sizes, T * F >= 2^31).  pdt_spec_augment_apply_warp(_elem) returns
+ *   PDT_E_UNSUPPORTED wherever this is not 1 with both grid flags 0.
+ *   pdt_spec_augment_apply_backward_elem: with a grid, on the general (scatter) form, a half type accumulates
+ *   in `workspace`, N * T * F floats the entry point zeroes itself, and rounds them into grad_feats in a
+ *   second launch; PDT_E_ARG when it is NULL or shorter.  Every other route ignores it.
+ *   pdt_spec_augment_backward_workspace_bytes: host only -- that size; has_grid: bit 0 a time grid, bit 1 a
+ *   frequency grid.  0 for float32, for no grid and for a time grid alone on a shape of the rows form (the
+ *   tensors taken as aligned to 8 bytes: ask pdt_spec_augment_apply_form with the addresses to be sure);
+ *   -1 for an element code that is not 0, 2 or 3 and for negative sizes. */
+int pdt_spec_augment_apply_elem(const void *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st,
+                                int64_t f_sf, const float *time_grid, const float *freq_grid, const int64_t *t_0,
+                                const int64_t *t_len, int64_t MT, const int64_t *f_0, const int64_t *f_len,
+                                int64_t MF, void *out, void *stream, int elem);
+int pdt_spec_augment_apply_warp_elem(const void *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st,
+                                     int64_t f_sf, const float *warp_src, const float *warp_flow,
+                                     const int64_t *lengths, int order, const int64_t *t_0, const int64_t *t_len,
+                                     int64_t MT, const int64_t *f_0, const int64_t *f_len, int64_t MF, void *out,
+                                     int32_t *bad_lengths, void *stream, int elem);
+int pdt_spec_augment_apply_backward_elem(const void *grad_out, int64_t N, int64_t T, int64_t F, const float *time_grid,
+                                         const float *freq_grid, const int64_t *t_0, const int64_t *t_len, int64_t MT,
+                                         const int64_t *f_0, const int64_t *f_len, int64_t MF, void *grad_feats,
+                                         void *stream, int elem, void *workspace, int64_t workspace_bytes);
+int64_t pdt_spec_augment_backward_workspace_bytes(int64_t N, int64_t T, int64_t F, int has_grid, int elem);
+int pdt_spec_augment_apply_form(int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st, int64_t f_sf,
+                                uint64_t in_addr, uint64_t out_addr, int has_time_grid, int has_freq_grid,
+                                int backward, int elem);
+
 int pdt_dense_image_warp_backward(const float *grad_out, const float *flow, int64_t N, int64_t C,
                                   int64_t H, int64_t W, int flow_is_hw, int mode, int padding,
                                   float *grad_image, void *stream);

@@ -142,6 +142,9 @@ extern "C" {
 //     pdt_ctc_lm_table_search_workspace_bytes returns 0 for sizes the search does not take
 //     then: pdt_concat_score, pdt_concat_score_backward, pdt_concat_score_workspace_bytes,
 //     pdt_concat_score_plan (csrc/concat_score.hip; no existing entry point changed)
+//     then: pdt_spec_augment_apply_elem, pdt_spec_augment_apply_warp_elem, pdt_spec_augment_apply_backward_elem
+//     (float16 / bfloat16 features as they are), pdt_spec_augment_apply_form and
+//     pdt_spec_augment_backward_workspace_bytes (host arithmetic only; no existing entry point changed)
 int pdt_amd_abi_version(void) { return 14; }
 
 int pdt_amd_set_switch(const char *name, int value) {

@@ -14,12 +14,15 @@
 
 namespace pdt {
 
-struct SpecAugArgs {
-  const float *feats; int64_t f_sn, f_st, f_sf;
+// E: the features' element type (float, f16_t, bf16_t: pdt_common.hpp).  The arithmetic is float32 for each;
+// a half element is widened exactly where it is read and rounded once (to nearest even) where it is stored.
+template <typename E>
+struct SpecAugArgsT {
+  const E *feats; int64_t f_sn, f_st, f_sf;  // strides in elements
   const float *tgrid, *fgrid;          // (N,T) / (N,F) normalised grids or null
   const int64_t *t0, *tl, *f0, *fl;    // (N,MT) / (N,MF) masks or null
   int N, T, F, MT, MF;
-  float *out;                          // (N,T,F) contiguous
+  E *out;                              // (N,T,F) contiguous
   // the time warp by its PARAMETERS instead of a grid (spec_augment_rows_kernel only): w_0, w (N,)
   // float and the lengths (N,) int64 (null: all T) -- the three-knot spline of warp_1d_grid is solved
   // in closed form and evaluated where the rows are planned, no (N, T) grid in memory
@@ -28,17 +31,59 @@ struct SpecAugArgs {
   // (_img.py:1037-1041) made where the lengths are read; device-visible memory the caller zeroed, or null
   int32_t *bad_lengths;
 };
+using SpecAugArgs = SpecAugArgsT<float>;
+
+// Four neighbouring elements as one access: 16 bytes of float32, 8 bytes of a half type.
+__device__ __forceinline__ float4 load4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 load4(const f16_t *p) {
+  typedef f16_t f16x4 __attribute__((ext_vector_type(4)));
+  const f16x4 h = *reinterpret_cast<const f16x4 *>(p);
+  return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
+}
+__device__ __forceinline__ float4 load4(const bf16_t *p) {
+  const uint2 u = *reinterpret_cast<const uint2 *>(p);
+  return make_float4(__uint_as_float(u.x << 16), __uint_as_float(u.x & 0xffff0000u), __uint_as_float(u.y << 16),
+                     __uint_as_float(u.y & 0xffff0000u));
+}
+// (elem_store's roundings, as bits: the float16 value is kept from being fused with a product in front of it)
+__device__ __forceinline__ unsigned half_bits(const f16_t *, float x) {
+  asm volatile("" : "+v"(x));
+  return (unsigned)__builtin_bit_cast(unsigned short, (f16_t)x);
+}
+__device__ __forceinline__ unsigned half_bits(const bf16_t *, float x) {
+  const unsigned u = __float_as_uint(x);
+  return x != x ? 0x7FC0u : ((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+template <typename E>
+__device__ __forceinline__ uint2 pack4(const E *tag, const float4 v) {
+  return make_uint2(half_bits(tag, v.x) | (half_bits(tag, v.y) << 16), half_bits(tag, v.z) | (half_bits(tag, v.w) << 16));
+}
+__device__ __forceinline__ void store4(float *p, const float4 v) { *reinterpret_cast<float4 *>(p) = v; }
+template <typename E>
+__device__ __forceinline__ void store4(E *p, const float4 v) { *reinterpret_cast<uint2 *>(p) = pack4(p, v); }
+// (non-temporal: written once, never read here -- apply 0.30 -> 0.29 ms on the box that measured both)
+__device__ __forceinline__ void store4_nt(float *p, const float4 v) {
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4 *>(p));
+}
+template <typename E>
+__device__ __forceinline__ void store4_nt(E *p, const float4 v) {
+  typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+  const uint2 u = pack4(p, v);
+  __builtin_nontemporal_store(u32x2{u.x, u.y}, reinterpret_cast<u32x2 *>(p));
+}
 
 
 // One pass: bilinear gather along time and frequency + band masks.  Workgroup = 256 threads
 // walking a contiguous range of (t, f) positions of one utterance.
-__global__ void __launch_bounds__(256) spec_augment_apply_kernel(const SpecAugArgs a, int tiles) {
+template <typename E>
+__global__ void __launch_bounds__(256) spec_augment_apply_kernel(const SpecAugArgsT<E> a, int tiles) {
   const int64_t n = blockIdx.x / tiles;
   const int tile = (int)(blockIdx.x % tiles);
   const int T = a.T, F = a.F;
   const int rows_per_tile = (T + tiles - 1) / tiles;
   const int t_begin = tile * rows_per_tile, t_end = min(T, t_begin + rows_per_tile);
-  const float *fn = a.feats + n * a.f_sn;
+  const E *fn = a.feats + n * a.f_sn;
   for (int idx = t_begin * F + (int)threadIdx.x; idx < t_end * F; idx += 256) {
     const int t = idx / F, f = idx - t * F;
     bool masked = false;
@@ -53,7 +98,7 @@ __global__ void __launch_bounds__(256) spec_augment_apply_kernel(const SpecAugAr
     float v = 0.0f;
     if (!masked) {
       if (!a.tgrid && !a.fgrid) {
-        v = fn[(int64_t)t * a.f_st + (int64_t)f * a.f_sf];
+        v = elem_load(fn + ((int64_t)t * a.f_st + (int64_t)f * a.f_sf));
       } else {
         // identity grids when only one axis is warped (:1173-1180)
         const float gy = a.tgrid ? a.tgrid[n * T + t] : (2.0f * (float)t + 1.0f) / (float)T - 1.0f;
@@ -62,26 +107,28 @@ __global__ void __launch_bounds__(256) spec_augment_apply_kernel(const SpecAugAr
         const float y0f = floorf(iy), x0f = floorf(ix);
         const int y0 = (int)y0f, x0 = (int)x0f, y1 = y0 + 1, x1 = x0 + 1;
         const float wy1 = iy - y0f, wx1 = ix - x0f, wy0 = (y0f + 1.0f) - iy, wx0 = (x0f + 1.0f) - ix;
-        const float *r0 = fn + (int64_t)y0 * a.f_st;
-        const float *r1 = fn + (int64_t)min(y1, T - 1) * a.f_st;
+        const E *r0 = fn + (int64_t)y0 * a.f_st;
+        const E *r1 = fn + (int64_t)min(y1, T - 1) * a.f_st;
         const int64_t c0 = (int64_t)x0 * a.f_sf, c1 = (int64_t)min(x1, F - 1) * a.f_sf;
         // taps outside the image carry weight 0 under border padding
-        v = r0[c0] * (wx0 * wy0);
-        if (x1 < F) v += r0[c1] * (wx1 * wy0);
-        if (y1 < T) v += r1[c0] * (wx0 * wy1);
-        if (x1 < F && y1 < T) v += r1[c1] * (wx1 * wy1);
+        v = elem_load(r0 + c0) * (wx0 * wy0);
+        if (x1 < F) v += elem_load(r0 + c1) * (wx1 * wy0);
+        if (y1 < T) v += elem_load(r1 + c0) * (wx0 * wy1);
+        if (x1 < F && y1 < T) v += elem_load(r1 + c1) * (wx1 * wy1);
       }
     }
-    a.out[(n * T + t) * (int64_t)F + f] = v;
+    elem_store(a.out + ((n * T + t) * (int64_t)F + f), v);
   }
 }
 
 // Fast path of the above for the common SpecAugment setting (no frequency warp, F % 4 == 0,
 // unit stride along F): an output row is a 2-tap blend of two source rows, so a thread moves
-// a float4 -- 16-byte coalesced loads and stores.  Per-row (source row, weights, time mask) and
-// per-column (frequency mask) decisions are made once per workgroup and kept in LDS.
+// four elements -- 16-byte coalesced loads and stores of float32, 8-byte ones of a half type.  Per-row
+// (source row, weights, time mask) and per-column (frequency mask) decisions are made once per workgroup
+// and kept in LDS.
 constexpr int kRowsPerTile = 256;
-__global__ void __launch_bounds__(256) spec_augment_rows_kernel(const SpecAugArgs a, int tiles) {
+template <typename E>
+__global__ void __launch_bounds__(256) spec_augment_rows_kernel(const SpecAugArgsT<E> a, int tiles) {
   __shared__ int row_y0[kRowsPerTile];      // source row, or -1 when the row is masked
   __shared__ float row_w1[kRowsPerTile];    // weight of source row y0 + 1
   __shared__ unsigned col_keep[64];         // per float4 column: 4 keep bits
@@ -133,8 +180,8 @@ __global__ void __launch_bounds__(256) spec_augment_rows_kernel(const SpecAugArg
     col_keep[c] = keep;
   }
   __syncthreads();
-  const float *fn = a.feats + n * a.f_sn;
-  float *on = a.out + n * (int64_t)T * a.F;
+  const E *fn = a.feats + n * a.f_sn;
+  E *on = a.out + n * (int64_t)T * a.F;
   const float inv = 1.0f / (float)F4;
   const int total = (t_end - t_begin) * F4;
   for (int idx = tid; idx < total; idx += 256) {
@@ -146,12 +193,12 @@ __global__ void __launch_bounds__(256) spec_augment_rows_kernel(const SpecAugArg
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (y0 >= 0) {
       const float w1 = row_w1[r];
-      const float4 r0 = *reinterpret_cast<const float4 *>(fn + (int64_t)y0 * a.f_st + 4 * f4);
+      const float4 r0 = load4(fn + (int64_t)y0 * a.f_st + 4 * f4);
       if (warped && y0 + 1 < T) {
         // same arithmetic as the 4-tap form with wx0 = 1, wx1 = 0; a row at y0 + 1 == T lies
         // outside the image and carries weight 0 under border padding
         const float w0 = ((float)y0 + 1.0f) - ((float)y0 + w1);
-        const float4 r1 = *reinterpret_cast<const float4 *>(fn + (int64_t)(y0 + 1) * a.f_st + 4 * f4);
+        const float4 r1 = load4(fn + (int64_t)(y0 + 1) * a.f_st + 4 * f4);
         v.x = r0.x * w0 + r1.x * w1;
         v.y = r0.y * w0 + r1.y * w1;
         v.z = r0.z * w0 + r1.z * w1;
@@ -168,18 +215,19 @@ __global__ void __launch_bounds__(256) spec_augment_rows_kernel(const SpecAugArg
       v.z = (keep & 4u) ? v.z : 0.0f;
       v.w = (keep & 8u) ? v.w : 0.0f;
     }
-    // (non-temporal: written once, never read here -- apply 0.30 -> 0.29 ms on the box that measured both)
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4 *>(on + (int64_t)(t_begin + r) * a.F + 4 * f4));
+    store4_nt(on + (int64_t)(t_begin + r) * a.F + 4 * f4, v);
   }
 }
 
 // Adjoint of the two kernels above with respect to the features: every unmasked output element
 // scatters its gradient to its (up to) four taps.  grad_feats is zeroed by the caller; the
 // accumulation uses the hardware float atomic (order of addition is not fixed, like
-// grid_sample's own backward).
+// grid_sample's own backward).  `grad_feats` is float32 whenever there is a grid -- a half element cannot
+// hold a running sum: for E a half type the caller's workspace, rounded once by round_rows_kernel -- and E
+// with no grid at all, where every element has its one writer.
+template <typename E>
 __global__ void __launch_bounds__(256)
-spec_augment_backward_kernel(const SpecAugArgs a, const float *__restrict__ grad_out,
+spec_augment_backward_kernel(const SpecAugArgsT<E> a, const E *__restrict__ grad_out,
                              float *__restrict__ grad_feats, int tiles) {
   const int64_t n = blockIdx.x / tiles;
   const int tile = (int)(blockIdx.x % tiles);
@@ -199,9 +247,11 @@ spec_augment_backward_kernel(const SpecAugArgs a, const float *__restrict__ grad
       masked = masked || (f >= s && f < s + a.fl[n * a.MF + m]);
     }
     if (masked) continue;
-    const float g = grad_out[(n * T + t) * (int64_t)F + f];
+    const float g = elem_load(grad_out + ((n * T + t) * (int64_t)F + f));
     if (!a.tgrid && !a.fgrid) {
-      gn[(int64_t)t * F + f] = g;  // one-to-one: no other writer
+      // one-to-one: no other writer (grad_feats is of E here)
+      if constexpr (sizeof(E) == sizeof(float)) gn[(int64_t)t * F + f] = g;
+      else elem_store(reinterpret_cast<E *>(grad_feats) + ((n * T + t) * (int64_t)F + f), g);
       continue;
     }
     const float gy = a.tgrid ? a.tgrid[n * T + t] : (2.0f * (float)t + 1.0f) / (float)T - 1.0f;
@@ -224,9 +274,10 @@ spec_augment_backward_kernel(const SpecAugArgs a, const float *__restrict__ grad
 // y0(t) = y - 1.  Warp grids are non-decreasing (warp_1d_grid pins both ends), so those rows
 // form one contiguous range found by binary search over the per-row table in LDS; for any
 // other grid the range degrades to all rows (still exact, just slower).
+template <typename E>
 __global__ void __launch_bounds__(256)
-spec_augment_rows_backward_kernel(const SpecAugArgs a, const float *__restrict__ grad_out,
-                                  float *__restrict__ grad_feats, int tiles) {
+spec_augment_rows_backward_kernel(const SpecAugArgsT<E> a, const E *__restrict__ grad_out,
+                                  E *__restrict__ grad_feats, int tiles) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int T = a.T, F4 = a.F >> 2;
   int *sy0 = reinterpret_cast<int *>(smem);             // [T] source row of output row t
@@ -291,8 +342,8 @@ spec_augment_rows_backward_kernel(const SpecAugArgs a, const float *__restrict__
     lb[i] = lo;
   }
   __syncthreads();
-  const float *gn = grad_out + n * (int64_t)T * a.F;
-  float *on = grad_feats + n * (int64_t)T * a.F;
+  const E *gn = grad_out + n * (int64_t)T * a.F;
+  E *on = grad_feats + n * (int64_t)T * a.F;
   const float inv = 1.0f / (float)F4;
   const int total = (y_e - y_b) * F4;
   for (int idx = tid; idx < total; idx += 256) {
@@ -305,7 +356,7 @@ spec_augment_rows_backward_kernel(const SpecAugArgs a, const float *__restrict__
       const int y0 = sy0[t];
       const float w = y0 == y ? sw0[t] : (y0 + 1 == y ? sw1[t] : 0.0f);
       if (w != 0.0f) {
-        const float4 g = *reinterpret_cast<const float4 *>(gn + (int64_t)t * a.F + 4 * f4);
+        const float4 g = load4(gn + (int64_t)t * a.F + 4 * f4);
         acc.x += g.x * w; acc.y += g.y * w; acc.z += g.z * w; acc.w += g.w * w;
       }
     }
@@ -314,8 +365,16 @@ spec_augment_rows_backward_kernel(const SpecAugArgs a, const float *__restrict__
     acc.y = (keep & 2u) ? acc.y : 0.0f;
     acc.z = (keep & 4u) ? acc.z : 0.0f;
     acc.w = (keep & 8u) ? acc.w : 0.0f;
-    *reinterpret_cast<float4 *>(on + (int64_t)y * a.F + 4 * f4) = acc;
+    store4(on + (int64_t)y * a.F + 4 * f4, acc);
   }
+}
+
+// The half scatter's last step: the float32 sums of the workspace, each rounded once into grad_feats.
+template <typename E>
+__global__ void __launch_bounds__(256) round_rows_kernel(const float *__restrict__ ws, E *__restrict__ grad_feats,
+                                                         int64_t total) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += step) elem_store(grad_feats + i, ws[i]);
 }
 
 
@@ -421,7 +480,8 @@ int pdt_spec_augment_draw(const float *u, int64_t N, int64_t R, const int64_t *l
 extern "C++" {
 // What the three application entry points check alike, in their order, and the fields they all fill.
 // `need`: the entry point's own pointers that must not be null.  False: return *rc (PDT_OK: nothing to do).
-static bool spec_aug_args(pdt::SpecAugArgs &a, int *rc, std::initializer_list<const void *> need, int64_t N,
+template <typename E>
+static bool spec_aug_args(pdt::SpecAugArgsT<E> &a, int *rc, std::initializer_list<const void *> need, int64_t N,
                           int64_t T, int64_t F, const int64_t *t_0, const int64_t *t_len, int64_t MT,
                           const int64_t *f_0, const int64_t *f_len, int64_t MF) {
   *rc = PDT_E_ARG;
@@ -440,18 +500,132 @@ static bool spec_aug_args(pdt::SpecAugArgs &a, int *rc, std::initializer_list<co
   return true;
 }
 
-// The rows kernels move float4s along F: F a multiple of 4 (at most 256: col_keep has 64 words), unit
-// stride along F, and every row of `in` and `out` 16-byte aligned.  The callers differ in what they know:
-// the forward entries pass the strides of a view; the adjoint's tensors are contiguous, (T * F, F, 1),
-// which F % 4 == 0 already aligns, and it adds its own LDS bound (three words per frame) at the call.
-// A frequency grid rules the rows kernels out; only pdt_spec_augment_apply_warp has none to check.
-static bool rows_layout_ok(int64_t F, int64_t f_sn, int64_t f_st, int64_t f_sf, const void *in, const void *out) {
-  return (F % 4 == 0) && F <= 256 && f_sf == 1 && (f_st % 4 == 0) && (f_sn % 4 == 0) &&
-         ((uintptr_t)in % 16 == 0) && ((uintptr_t)out % 16 == 0);
+// The rows kernels move four elements along F as one access (16 bytes of float32, 8 of a half type): F a
+// multiple of 4 (at most 256: col_keep has 64 words), unit stride along F, and every row of `in` and `out`
+// aligned to those 4 * esz bytes.  The callers differ in what they know: the forward entries pass the
+// strides of a view; the adjoint's tensors are contiguous, (T * F, F, 1), which F % 4 == 0 already aligns,
+// and it adds its own LDS bound (three words per frame).  A frequency grid rules the rows kernels out.
+static bool rows_layout_ok(size_t esz, int64_t F, int64_t f_sn, int64_t f_st, int64_t f_sf, uint64_t in, uint64_t out) {
+  return (F % 4 == 0) && F <= 256 && f_sf == 1 && (f_st % 4 == 0) && (f_sn % 4 == 0) && (in % (4 * esz) == 0) &&
+         (out % (4 * esz) == 0);
 }
+static size_t rows_backward_smem(int64_t T) { return (size_t)T * 12 + 260 * 4 + 64 * 4; }
 static unsigned rows_tiles(int64_t T) { return (unsigned)((T + pdt::kRowsPerTile - 1) / pdt::kRowsPerTile); }
 // ~16K elements per workgroup keeps >= 8 workgroups per CU in flight at N = 2048
 static unsigned elem_tiles(int64_t T, int64_t F) { return (unsigned)std::max<int64_t>((T * F + 16383) / 16384, 1); }
+}  // extern "C++"
+
+int pdt_spec_augment_apply_form(int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st, int64_t f_sf,
+                                uint64_t in_addr, uint64_t out_addr, int has_time_grid, int has_freq_grid,
+                                int backward, int elem) {
+  (void)has_time_grid;  // (a time grid is served by either form)
+  const int es = pdt::elem_status(elem);
+  if (es != PDT_OK) return es;
+  if (N < 0 || T < 0 || F < 0) return PDT_E_ARG;
+  if (T * F >= (1ll << 31) || N > 0x7fffffffll) return PDT_E_TOO_LONG;
+  const size_t esz = elem == 0 ? 4 : 2;
+  if (has_freq_grid) return 0;
+  if (backward) return rows_layout_ok(esz, F, T * F, F, 1, in_addr, out_addr) && rows_backward_smem(T) <= 64 * 1024;
+  return rows_layout_ok(esz, F, f_sn, f_st, f_sf, in_addr, out_addr);
+}
+
+int64_t pdt_spec_augment_backward_workspace_bytes(int64_t N, int64_t T, int64_t F, int has_grid, int elem) {
+  if (pdt::elem_status(elem) != PDT_OK || N < 0 || T < 0 || F < 0) return -1;
+  if (elem == 0 || has_grid == 0) return 0;  // float32 accumulates in grad_feats; no grid: one writer per element
+  if (!(has_grid & 2) && pdt_spec_augment_apply_form(N, T, F, T * F, F, 1, 0, 0, 1, 0, 1, elem) == 1) return 0;
+  return 4 * N * T * F;
+}
+
+extern "C++" {
+template <typename E>
+static int apply_impl(int elem, const E *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st,
+                      int64_t f_sf, const float *time_grid, const float *freq_grid, const int64_t *t_0,
+                      const int64_t *t_len, int64_t MT, const int64_t *f_0, const int64_t *f_len, int64_t MF, E *out,
+                      void *stream) {
+  using namespace pdt;
+  SpecAugArgsT<E> a{};
+  int rc;
+  if (!spec_aug_args(a, &rc, {feats, out}, N, T, F, t_0, t_len, MT, f_0, f_len, MF)) return rc;
+  a.feats = feats; a.f_sn = f_sn; a.f_st = f_st; a.f_sf = f_sf; a.out = out;
+  a.tgrid = time_grid; a.fgrid = freq_grid;
+  const int form = pdt_spec_augment_apply_form(N, T, F, f_sn, f_st, f_sf, (uint64_t)(uintptr_t)feats,
+                                               (uint64_t)(uintptr_t)out, time_grid != nullptr,
+                                               freq_grid != nullptr, 0, elem);
+  if (form < 0) return form;
+  if (form == 1) {
+    const unsigned rtiles = rows_tiles(T);
+    hipLaunchKernelGGL(spec_augment_rows_kernel<E>, dim3((unsigned)N * rtiles), dim3(256), 0, (hipStream_t)stream, a,
+                       (int)rtiles);
+  } else {
+    const unsigned tiles = elem_tiles(T, F);
+    hipLaunchKernelGGL(spec_augment_apply_kernel<E>, dim3((unsigned)N * tiles), dim3(256), 0, (hipStream_t)stream, a,
+                       (int)tiles);
+  }
+  return (int)hipGetLastError();
+}
+
+template <typename E>
+static int apply_warp_impl(int elem, const E *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st,
+                           int64_t f_sf, const float *warp_src, const float *warp_flow, const int64_t *lengths,
+                           int order, const int64_t *t_0, const int64_t *t_len, int64_t MT, const int64_t *f_0,
+                           const int64_t *f_len, int64_t MF, E *out, int32_t *bad_lengths, void *stream) {
+  using namespace pdt;
+  if (order < 1) return PDT_E_ARG;
+  SpecAugArgsT<E> a{};
+  int rc;
+  if (!spec_aug_args(a, &rc, {feats, out, warp_src, warp_flow}, N, T, F, t_0, t_len, MT, f_0, f_len, MF)) return rc;
+  const int form = pdt_spec_augment_apply_form(N, T, F, f_sn, f_st, f_sf, (uint64_t)(uintptr_t)feats,
+                                               (uint64_t)(uintptr_t)out, 0, 0, 0, elem);
+  if (form < 0) return form;
+  if (form != 1) return PDT_E_UNSUPPORTED;
+  a.feats = feats; a.f_sn = f_sn; a.f_st = f_st; a.f_sf = f_sf; a.out = out;
+  a.tw_src = warp_src; a.tw_flow = warp_flow; a.tw_len = lengths; a.tw_order = order;
+  a.bad_lengths = lengths ? bad_lengths : nullptr;
+  const unsigned rtiles = rows_tiles(T);
+  hipLaunchKernelGGL(spec_augment_rows_kernel<E>, dim3((unsigned)N * rtiles), dim3(256), 0, (hipStream_t)stream, a,
+                     (int)rtiles);
+  return (int)hipGetLastError();
+}
+
+// `workspace`: N * T * F floats for a half E on the scatter route with a grid (zeroed here); unused otherwise.
+template <typename E>
+static int apply_backward_impl(int elem, const E *grad_out, int64_t N, int64_t T, int64_t F, const float *time_grid,
+                               const float *freq_grid, const int64_t *t_0, const int64_t *t_len, int64_t MT,
+                               const int64_t *f_0, const int64_t *f_len, int64_t MF, E *grad_feats, void *workspace,
+                               int64_t workspace_bytes, void *stream) {
+  using namespace pdt;
+  SpecAugArgsT<E> a{};
+  int rc;
+  if (!spec_aug_args(a, &rc, {grad_out, grad_feats}, N, T, F, t_0, t_len, MT, f_0, f_len, MF)) return rc;
+  a.tgrid = time_grid; a.fgrid = freq_grid;
+  const int form = pdt_spec_augment_apply_form(N, T, F, T * F, F, 1, (uint64_t)(uintptr_t)grad_out,
+                                               (uint64_t)(uintptr_t)grad_feats, time_grid != nullptr,
+                                               freq_grid != nullptr, 1, elem);
+  if (form < 0) return form;
+  if (form == 1) {
+    const unsigned rtiles = rows_tiles(T);
+    hipLaunchKernelGGL(spec_augment_rows_backward_kernel<E>, dim3((unsigned)N * rtiles), dim3(256),
+                       rows_backward_smem(T), (hipStream_t)stream, a, grad_out, grad_feats, (int)rtiles);
+    return (int)hipGetLastError();
+  }
+  const int64_t total = N * T * F;
+  const bool sums = sizeof(E) != sizeof(float) && (time_grid || freq_grid);  // float32 sums, rounded afterwards
+  if (sums && (!workspace || workspace_bytes < total * (int64_t)sizeof(float))) return PDT_E_ARG;
+  float *acc = sums ? (float *)workspace : reinterpret_cast<float *>(grad_feats);
+  hipError_t e = hipMemsetAsync(acc, 0, (size_t)total * (sums ? sizeof(float) : sizeof(E)), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+  const unsigned tiles = elem_tiles(T, F);
+  hipLaunchKernelGGL(spec_augment_backward_kernel<E>, dim3((unsigned)N * tiles), dim3(256), 0, (hipStream_t)stream, a,
+                     grad_out, acc, (int)tiles);
+  if constexpr (sizeof(E) != sizeof(float)) {
+    if (sums) {
+      const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 1 << 16);
+      hipLaunchKernelGGL(round_rows_kernel<E>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
+                         (const float *)workspace, grad_feats, total);
+    }
+  }
+  return (int)hipGetLastError();
+}
 }  // extern "C++"
 
 int pdt_spec_augment_apply(const float *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn,
@@ -459,22 +633,8 @@ int pdt_spec_augment_apply(const float *feats, int64_t N, int64_t T, int64_t F, 
                            const float *freq_grid, const int64_t *t_0, const int64_t *t_len,
                            int64_t MT, const int64_t *f_0, const int64_t *f_len, int64_t MF,
                            float *out, void *stream) {
-  using namespace pdt;
-  SpecAugArgs a{};
-  int rc;
-  if (!spec_aug_args(a, &rc, {feats, out}, N, T, F, t_0, t_len, MT, f_0, f_len, MF)) return rc;
-  a.feats = feats; a.f_sn = f_sn; a.f_st = f_st; a.f_sf = f_sf; a.out = out;
-  a.tgrid = time_grid; a.fgrid = freq_grid;
-  if (!freq_grid && rows_layout_ok(F, f_sn, f_st, f_sf, feats, out)) {
-    const unsigned rtiles = rows_tiles(T);
-    hipLaunchKernelGGL(spec_augment_rows_kernel, dim3((unsigned)N * rtiles), dim3(256), 0, (hipStream_t)stream, a,
-                       (int)rtiles);
-  } else {
-    const unsigned tiles = elem_tiles(T, F);
-    hipLaunchKernelGGL(spec_augment_apply_kernel, dim3((unsigned)N * tiles), dim3(256), 0, (hipStream_t)stream, a,
-                       (int)tiles);
-  }
-  return (int)hipGetLastError();
+  return apply_impl<float>(0, feats, N, T, F, f_sn, f_st, f_sf, time_grid, freq_grid, t_0, t_len, MT, f_0, f_len, MF,
+                           out, stream);
 }
 
 int pdt_spec_augment_apply_warp(const float *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn,
@@ -483,19 +643,8 @@ int pdt_spec_augment_apply_warp(const float *feats, int64_t N, int64_t T, int64_
                                 const int64_t *t_len, int64_t MT, const int64_t *f_0,
                                 const int64_t *f_len, int64_t MF, float *out, int32_t *bad_lengths,
                                 void *stream) {
-  using namespace pdt;
-  if (order < 1) return PDT_E_ARG;
-  SpecAugArgs a{};
-  int rc;
-  if (!spec_aug_args(a, &rc, {feats, out, warp_src, warp_flow}, N, T, F, t_0, t_len, MT, f_0, f_len, MF)) return rc;
-  if (!rows_layout_ok(F, f_sn, f_st, f_sf, feats, out)) return PDT_E_UNSUPPORTED;
-  a.feats = feats; a.f_sn = f_sn; a.f_st = f_st; a.f_sf = f_sf; a.out = out;
-  a.tw_src = warp_src; a.tw_flow = warp_flow; a.tw_len = lengths; a.tw_order = order;
-  a.bad_lengths = lengths ? bad_lengths : nullptr;
-  const unsigned rtiles = rows_tiles(T);
-  hipLaunchKernelGGL(spec_augment_rows_kernel, dim3((unsigned)N * rtiles), dim3(256), 0, (hipStream_t)stream, a,
-                     (int)rtiles);
-  return (int)hipGetLastError();
+  return apply_warp_impl<float>(0, feats, N, T, F, f_sn, f_st, f_sf, warp_src, warp_flow, lengths, order, t_0, t_len,
+                                MT, f_0, f_len, MF, out, bad_lengths, stream);
 }
 
 int pdt_spec_augment_apply_backward(const float *grad_out, int64_t N, int64_t T, int64_t F,
@@ -503,24 +652,46 @@ int pdt_spec_augment_apply_backward(const float *grad_out, int64_t N, int64_t T,
                                     const int64_t *t_0, const int64_t *t_len, int64_t MT,
                                     const int64_t *f_0, const int64_t *f_len, int64_t MF,
                                     float *grad_feats, void *stream) {
-  using namespace pdt;
-  SpecAugArgs a{};
-  int rc;
-  if (!spec_aug_args(a, &rc, {grad_out, grad_feats}, N, T, F, t_0, t_len, MT, f_0, f_len, MF)) return rc;
-  a.tgrid = time_grid; a.fgrid = freq_grid;
-  const size_t rows_smem = (size_t)T * 12 + 260 * 4 + 64 * 4;
-  if (!freq_grid && rows_layout_ok(F, T * F, F, 1, grad_out, grad_feats) && rows_smem <= 64 * 1024) {
-    const unsigned rtiles = rows_tiles(T);
-    hipLaunchKernelGGL(spec_augment_rows_backward_kernel, dim3((unsigned)N * rtiles), dim3(256), rows_smem,
-                       (hipStream_t)stream, a, grad_out, grad_feats, (int)rtiles);
-    return (int)hipGetLastError();
-  }
-  hipError_t e = hipMemsetAsync(grad_feats, 0, (size_t)(N * T * F) * sizeof(float), (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  const unsigned tiles = elem_tiles(T, F);
-  hipLaunchKernelGGL(spec_augment_backward_kernel, dim3((unsigned)N * tiles), dim3(256), 0, (hipStream_t)stream, a,
-                     grad_out, grad_feats, (int)tiles);
-  return (int)hipGetLastError();
+  return apply_backward_impl<float>(0, grad_out, N, T, F, time_grid, freq_grid, t_0, t_len, MT, f_0, f_len, MF,
+                                    grad_feats, nullptr, 0, stream);
 }
 
+// The same three on features of element type `elem` (0 float32: the launch above; 2 float16; 3 bfloat16).
+// The element code is judged first; CALL names the element type as E.
+#define PDT_SPEC_ELEM(CALL)                                \
+  {                                                        \
+    const int es_ = pdt::elem_status(elem);                \
+    if (es_ != PDT_OK) return es_;                         \
+  }                                                        \
+  if (elem == 2) { using E = pdt::f16_t; return CALL; }    \
+  if (elem == 3) { using E = pdt::bf16_t; return CALL; }   \
+  { using E = float; return CALL; }
+
+int pdt_spec_augment_apply_elem(const void *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st,
+                                int64_t f_sf, const float *time_grid, const float *freq_grid, const int64_t *t_0,
+                                const int64_t *t_len, int64_t MT, const int64_t *f_0, const int64_t *f_len,
+                                int64_t MF, void *out, void *stream, int elem) {
+  PDT_SPEC_ELEM((apply_impl<E>(elem, (const E *)feats, N, T, F, f_sn, f_st, f_sf, time_grid, freq_grid, t_0, t_len, MT,
+                               f_0, f_len, MF, (E *)out, stream)))
+}
+
+int pdt_spec_augment_apply_warp_elem(const void *feats, int64_t N, int64_t T, int64_t F, int64_t f_sn, int64_t f_st,
+                                     int64_t f_sf, const float *warp_src, const float *warp_flow,
+                                     const int64_t *lengths, int order, const int64_t *t_0, const int64_t *t_len,
+                                     int64_t MT, const int64_t *f_0, const int64_t *f_len, int64_t MF, void *out,
+                                     int32_t *bad_lengths, void *stream, int elem) {
+  PDT_SPEC_ELEM((apply_warp_impl<E>(elem, (const E *)feats, N, T, F, f_sn, f_st, f_sf, warp_src, warp_flow, lengths,
+                                    order, t_0, t_len, MT, f_0, f_len, MF, (E *)out, bad_lengths, stream)))
+}
+
+int pdt_spec_augment_apply_backward_elem(const void *grad_out, int64_t N, int64_t T, int64_t F, const float *time_grid,
+                                         const float *freq_grid, const int64_t *t_0, const int64_t *t_len, int64_t MT,
+                                         const int64_t *f_0, const int64_t *f_len, int64_t MF, void *grad_feats,
+                                         void *stream, int elem, void *workspace, int64_t workspace_bytes) {
+  PDT_SPEC_ELEM((apply_backward_impl<E>(elem, (const E *)grad_out, N, T, F, time_grid, freq_grid, t_0, t_len, MT, f_0,
+                                        f_len, MF, (E *)grad_feats, workspace, workspace_bytes, stream)))
+}
+#undef PDT_SPEC_ELEM
+
 }  // extern "C"
+

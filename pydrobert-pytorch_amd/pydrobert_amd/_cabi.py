@@ -36,7 +36,10 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # which keep their declarations) with the host-only pdt_ctc_prefix_search_wide_plan, and the same for the
 # hard-OCD loss (pdt_ocd_loss_forward_elem, pdt_ocd_loss_backward_elem) and the attention entry points
 # (pdt_attn_workspace_bytes_elem, pdt_attn_dot_elem, pdt_attn_dot_backward_elem, pdt_attn_pool_elem,
-# pdt_attn_pool_backward_elem: the five without the suffix keep refusing every dtype code but 0 and 1).
+# pdt_attn_pool_backward_elem: the five without the suffix keep refusing every dtype code but 0 and 1) and
+# SpecAugment's application (pdt_spec_augment_apply_elem, pdt_spec_augment_apply_warp_elem,
+# pdt_spec_augment_apply_backward_elem) with the host-only pdt_spec_augment_apply_form and
+# pdt_spec_augment_backward_workspace_bytes.
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -186,6 +189,23 @@ SIGNATURES = {
     "pdt_spec_augment_apply_backward": (
         _INT,
         [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P],
+    ),
+    "pdt_spec_augment_apply_elem": (
+        _INT,
+        [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _INT],
+    ),
+    "pdt_spec_augment_apply_warp_elem": (
+        _INT,
+        [_P, _I64, _I64, _I64, _I64, _I64, _I64, _P, _P, _P, _INT, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _INT],
+    ),
+    "pdt_spec_augment_apply_backward_elem": (
+        _INT,
+        [_P, _I64, _I64, _I64, _P, _P, _P, _P, _I64, _P, _P, _I64, _P, _P, _INT, _P, _I64],
+    ),
+    "pdt_spec_augment_backward_workspace_bytes": (_I64, [_I64, _I64, _I64, _INT, _INT]),
+    "pdt_spec_augment_apply_form": (
+        # (in_addr, out_addr: uint64_t in the header; user-space addresses are below 2^63, the same 8 bytes)
+        _INT, [_I64, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _INT, _INT, _INT, _INT],
     ),
     "pdt_dense_image_warp_backward": (
         _INT,

@@ -1086,6 +1086,22 @@ def _spec_augment_draw(
             out[4] if tm else none, out[5] if tm else none, out[6] if fm else none, out[7] if fm else none)  # fmt: skip
 
 
+# float16 / bfloat16 features go to the kernels as they are (include/pdt_amd.h: the ``_elem`` entry points'
+# element codes); the arithmetic is float32 and a result is rounded once where it is stored
+_HALF_ELEM = {torch.float16: 2, torch.bfloat16: 3}
+
+
+def _spec_feats(feats: torch.Tensor) -> Tuple[torch.Tensor, Optional[int]]:
+    """``(x, elem)``: the detached features the application kernels read, with their own strides -- float16 /
+    bfloat16 untouched with their element code, float32 untouched with None (the entry points without the
+    suffix), anything else as float32."""
+    x = feats.detach()
+    elem = _HALF_ELEM.get(x.dtype)
+    if elem is None and x.dtype != torch.float:
+        x = x.float()
+    return x, elem
+
+
 def _has(a: Optional[torch.Tensor], b: Optional[torch.Tensor]) -> bool:
     return a is not None and a.numel() > 0 and b is not None and b.numel() > 0
 
@@ -1104,17 +1120,19 @@ def _spec_augment_apply_op(
     ``feats`` (csrc/spec_augment.hip)."""
     device = _cabi.require_hip(feats, tgrid, fgrid, t_0, t, f_0, f)
     N, T, F = feats.shape
-    x = feats.detach()
-    if x.dtype != torch.float:
-        x = x.float()
+    x, elem = _spec_feats(feats)
     mt, mf = _mask_counts(t_0, f_0)
     with torch.cuda.device(device):
-        out = torch.empty((N, T, F), device=device, dtype=torch.float)
-        rc = _cabi.lib().pdt_spec_augment_apply(
+        out = torch.empty((N, T, F), device=device, dtype=x.dtype)
+        args = (
             _cabi.ptr(x), N, T, F, x.stride(0), x.stride(1), x.stride(2),
             _cabi.ptr(tgrid), _cabi.ptr(fgrid), _cabi.ptr(t_0), _cabi.ptr(t), mt,
             _cabi.ptr(f_0), _cabi.ptr(f), mf, _cabi.ptr(out), _cabi.stream_ptr(device),
         )  # fmt: skip
+        if elem is None:
+            rc = _cabi.lib().pdt_spec_augment_apply(*args)
+        else:
+            rc = _cabi.lib().pdt_spec_augment_apply_elem(*args, elem)
     _cabi.check(rc, "pdt_spec_augment_apply")
     return out.to(feats.dtype)
 
@@ -1137,16 +1155,29 @@ def _spec_augment_apply_backward_op(
     """Adjoint of ``spec_augment_apply`` with respect to the features (masked positions carry
     no gradient; the others scatter theirs to their taps)."""
     device = _cabi.require_hip(grad_out, tgrid, fgrid, t_0, t, f_0, f)
-    g = _f32c(grad_out)
+    elem = _HALF_ELEM.get(grad_out.dtype)
+    g = _f32c(grad_out) if elem is None else grad_out.detach().contiguous()
     N, T, F = g.shape
     mt, mf = _mask_counts(t_0, f_0)
+    L = _cabi.lib()
     with torch.cuda.device(device):
         grad = torch.empty_like(g)
-        rc = _cabi.lib().pdt_spec_augment_apply_backward(
+        args = (
             _cabi.ptr(g), N, T, F, _cabi.ptr(tgrid), _cabi.ptr(fgrid), _cabi.ptr(t_0),
             _cabi.ptr(t), mt, _cabi.ptr(f_0), _cabi.ptr(f), mf, _cabi.ptr(grad),
             _cabi.stream_ptr(device),
         )  # fmt: skip
+        if elem is None:
+            rc = L.pdt_spec_augment_apply_backward(*args)
+        else:
+            # (sums of several taps are float32: the scatter form accumulates in a workspace and rounds once)
+            ws = None
+            if (tgrid is not None or fgrid is not None) and g.numel() and L.pdt_spec_augment_apply_form(
+                N, T, F, T * F, F, 1, g.data_ptr(), grad.data_ptr(), int(tgrid is not None), int(fgrid is not None),
+                1, elem,
+            ) == 0:  # fmt: skip
+                ws = torch.empty((N, T, F), device=device, dtype=torch.float)
+            rc = L.pdt_spec_augment_apply_backward_elem(*args, elem, _cabi.ptr(ws), 0 if ws is None else 4 * ws.numel())
     _cabi.check(rc, "pdt_spec_augment_apply_backward")
     return grad.to(grad_out.dtype)
 
@@ -1157,7 +1188,7 @@ def _(grad_out, tgrid, fgrid, t_0, t, f_0, f):
 
 
 def _launch_apply_warp(device, x, src, flow, lens, order, t_0, t, mt, f_0, f, mf, check_lengths) -> Optional[torch.Tensor]:
-    """One launch of ``pdt_spec_augment_apply_warp`` on float features ``x``: the result, or None for a
+    """One launch of ``pdt_spec_augment_apply_warp`` (``_elem`` for half features) on ``x``: the result, or None for a
     layout the one-pass kernel does not take (the caller goes through the grid).
 
     ``check_lengths``: the reference's "values of lengths must be between (1, T)" (_img.py:1037-1041)
@@ -1166,12 +1197,16 @@ def _launch_apply_warp(device, x, src, flow, lens, order, t_0, t, mt, f_0, f, mf
     N, T, F = x.shape
     report = _cabi.host_report(device) if (check_lengths and lens is not None) else None
     with torch.cuda.device(device):
-        out = torch.empty((N, T, F), device=device, dtype=torch.float)
-        rc = _cabi.lib().pdt_spec_augment_apply_warp(
+        out = torch.empty((N, T, F), device=device, dtype=x.dtype)
+        args = (
             _cabi.ptr(x), N, T, F, x.stride(0), x.stride(1), x.stride(2), _cabi.ptr(src), _cabi.ptr(flow),
             _cabi.ptr(lens), int(order), _cabi.ptr(t_0), _cabi.ptr(t), mt, _cabi.ptr(f_0), _cabi.ptr(f), mf,
             _cabi.ptr(out), 0 if report is None else report.ptr, _cabi.stream_ptr(device),
         )  # fmt: skip
+        if x.dtype == torch.float:
+            rc = _cabi.lib().pdt_spec_augment_apply_warp(*args)
+        else:
+            rc = _cabi.lib().pdt_spec_augment_apply_warp_elem(*args, _HALF_ELEM[x.dtype])
     if report is not None and (rc or not (N and T and F)):
         report.disarm()  # (no kernel was launched)
     if rc == _cabi.PDT_E_UNSUPPORTED:
@@ -1203,9 +1238,7 @@ def _spec_augment_apply_warp_op(
     Layouts the one-pass kernel does not take go through the grid as before."""
     device = _cabi.require_hip(feats, w_0, w, lengths, t_0, t, f_0, f)
     N, T, F = feats.shape
-    x = feats.detach()
-    if x.dtype != torch.float:
-        x = x.float()
+    x, _ = _spec_feats(feats)
     src, flow = _f32c(w_0), _f32c(w)
     lens = _lens_long(lengths)
     mt, mf = _mask_counts(t_0, f_0)
@@ -1264,9 +1297,7 @@ def _spec_augment_forward_op(
     ``[out, w_0, w, t_0, t, f_0, f]`` (the parameters for the adjoint; disabled masks: zero elements)."""
     device = _cabi.require_hip(feats, uniforms, lengths)
     N, T, F = feats.shape
-    x = feats.detach()
-    if x.dtype != torch.float:
-        x = x.float()
+    x, _ = _spec_feats(feats)
     u = uniforms.detach()
     if u.dtype != torch.float or not u.is_contiguous():
         u = u.float().contiguous()

@@ -75,6 +75,9 @@ struct CtcArgs {
   // PDT_CTC_TWOFRAME=0: the two-frames-per-pass instance decides every frame by itself, none in pairs by
   // ctc_two_steady_frames (same results, same kernel instance; the tests compare the two)
   int no_twoframe;
+  // PDT_CTC_PACE=0: the producers of the one-producer forms stay at issue priority 0, none follows its own
+  // progress (ctc_ring.hpp: pace_prio; same results, same kernel instance)
+  int no_pace;
 };
 
 struct Beam {

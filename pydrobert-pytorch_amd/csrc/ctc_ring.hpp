@@ -19,8 +19,42 @@
 #ifndef PDT_CONSUMER_PRIO
 #define PDT_CONSUMER_PRIO 3
 #endif
+// Pacing (one-producer forms of ctc_search.hip; PDT_CTC_PACE=0 / CtcArgs::no_pace: off).  Every wave of the
+// launch is resident at once and the SIMDs issue the oldest wave first, so left alone the producers of the
+// workgroups dispatched first get the issue slots, their utterances leave early, and the youngest quarter ends
+// the launch two waves to a SIMD (EXPERIMENTS.md sections 10.12, 19.1).  A paced producer's issue priority
+// cycles with its own frame counter: one step down per band of PDT_PACE_BAND frames (a power of two) -- 2, 1, 0
+// and round again; level 3 stays the consumers'.  Measured: cycling the levels breaks the oldest-first order
+// among the producers and the utterances' loops end closer together (last over first 1.43 -> 1.18); a fixed
+// level does a third of that, and bands of 4 to 64 frames do the same, so it is the cycling that matters, not
+// which producer is how far ahead.  Only launches whose whole grid is resident are paced (launch_ctc_search_p).
+#ifndef PDT_PACE_BAND
+#define PDT_PACE_BAND 64
+#endif
 
 namespace pdt {
+
+// the level of the band frame t lies in: scalar arithmetic, a branch and s_setprio with an immediate operand;
+// no vector instruction.  (-DPDT_NO_PRIO: nothing, like every other s_setprio of the searches.)
+__device__ __forceinline__ void pace_prio(const int t) {
+#ifndef PDT_NO_PRIO
+  const unsigned band = ((unsigned)t / PDT_PACE_BAND) % 3u;
+  if (band == 0)
+    __builtin_amdgcn_s_setprio(2);
+  else if (band == 1)
+    __builtin_amdgcn_s_setprio(1);
+  else
+    __builtin_amdgcn_s_setprio(0);
+#else
+  (void)t;
+#endif
+}
+// a paced wave that has to wait polls at level 0, like every wave of the search that waits
+__device__ __forceinline__ void pace_prio_polling() {
+#ifndef PDT_NO_PRIO
+  __builtin_amdgcn_s_setprio(0);
+#endif
+}
 
 // exp(x) for x <= 0 (softmax numerators): OCML's expf without its overflow / underflow guards --
 // the same hi/lo range reduction around v_exp_f32; v_ldexp_f32 flushes what underflows.

@@ -179,8 +179,17 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
       }
       for (int t = 0, sl = 0; t < Tn; t += 2, sl ^= 2) {
         // both slots free: at most NS frames in flight (NS = 4: the consumer holds the previous pair)
-        while (t + 1 - __hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= NS)
-          __builtin_amdgcn_s_sleep(2);
+        // (paced -- ctc_ring.hpp: pace_prio -- the level follows the frame: set at a band's first pass, and after
+        // a wait, which is spent at level 0 like every wait of the search; the switch in the outer conditions)
+        if (t + 1 - __hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= NS) {
+          if (!a.no_pace) pace_prio_polling();
+          do {
+            __builtin_amdgcn_s_sleep(2);
+          } while (t + 1 - __hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= NS);
+          if (!a.no_pace) pace_prio(t);
+        } else if ((t & (PDT_PACE_BAND - 1)) == 0 && !a.no_pace) {
+          pace_prio(t);
+        }
         unsigned char *sb = my_ring + sl * rl.slot_bytes;
         float *p = reinterpret_cast<float *>(sb);
         int *tl_tok = reinterpret_cast<int *>(sb + row_bytes);
@@ -338,8 +347,18 @@ ctc_search_kernel(const CtcArgs a, const RingLayout rl_arg) {
     int sl = pr % NS;  // t % NS, kept by add / compare: no division in the loop
     for (int t = pr; t < Tn; t += P, sl = sl + P >= NS ? sl + P - NS : sl + P) {
       // wait for the slot to be free: at most NS frames in flight
-      while (t - __hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= NS)
-        __builtin_amdgcn_s_sleep(2);
+      // (the one-producer forms are paced like the two-frame producer above; several producers per utterance
+      // take frames in turn and are bound by their rows' loads, not by issue slots: they stay at level 0)
+      const bool paced = P == 1 && !a.no_pace;
+      if (t - __hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= NS) {
+        if (paced) pace_prio_polling();
+        do {
+          __builtin_amdgcn_s_sleep(2);
+        } while (t - __hip_atomic_load(consumed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= NS);
+        if (paced) pace_prio(t);
+      } else if ((t & (PDT_PACE_BAND - 1)) == 0 && paced) {
+        pace_prio(t);
+      }
       float *p = slot_row(sl);
       int *tl_tok = slot_tok(sl);
       unsigned char *pos = slot_pos(sl);
@@ -810,8 +829,33 @@ static int launch_ctc_search_p(const CtcArgs &a, const RingLayout &rl, hipStream
   const size_t smem = (size_t)rl.utt_bytes * rl.utt_per_wg;
   if (const int rc = set_lds(ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR, E>, smem)) return rc;
   const unsigned grid = (unsigned)((a.N + rl.utt_per_wg - 1) / rl.utt_per_wg);
-  hipLaunchKernelGGL((ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR, E>), dim3(grid), dim3(64 * (P + 1) * rl.utt_per_wg), smem,
-                     stream, a, rl);
+  const int threads = 64 * (P + 1) * rl.utt_per_wg;
+  CtcArgs paced = a;
+  if (P == 1 && !paced.no_pace) {
+    // Pacing makes the resident workgroups end together, which pays only when none waits behind them: with
+    // more workgroups than the device holds at once, the slots of the early leavers are what starts the rest
+    // (measured at N = 6144, one and a half times the headline: paced +4.4 %; EXPERIMENTS.md section 19.1).
+    // Host arithmetic, asked once per instance, device and LDS size.
+    static thread_local size_t asked_smem = ~(size_t)0;
+    static thread_local int asked_dev = -1;
+    static thread_local unsigned resident = 0;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+    if (asked_smem != smem || asked_dev != dev) {
+      int cus = 0, per_cu = 0;
+      asked_dev = dev;
+      if (dev >= 0 &&
+          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR, E>, threads, smem) == hipSuccess)
+        resident = (unsigned)(cus * per_cu);
+      else
+        resident = 0;
+      asked_smem = smem;
+    }
+    if (grid > resident) paced.no_pace = 1;
+  }
+  hipLaunchKernelGGL((ctc_search_kernel<P, NT, INREG, GROW, WC, VC, PAIR, E>), dim3(grid), dim3(threads), smem,
+                     stream, paced, rl);
   return (int)hipGetLastError();
 }
 
@@ -956,6 +1000,7 @@ int pdt_ctc_prefix_search_elem(const void *logits, int64_t T, int64_t N, int64_t
   a.no_lean_extra = switches().ctc_lean_extra == 0 ? 1 : 0;
   a.no_steady = switches().ctc_steady == 0 ? 1 : 0;  // (no part of the plan: both values take the same instance)
   a.no_twoframe = (switches().ctc_twoframe == 0 || a.no_steady) ? 1 : 0;  // (likewise)
+  a.no_pace = switches().ctc_pace == 0 ? 1 : 0;  // (likewise)
   // (contiguous rows: the register form addresses a row as base + immediates)
   if (ctc_rowreg_applies(a.V, a.W) && lg_sv == 1) return launch_ctc_rowreg(a, (hipStream_t)stream, elem);
   CtcPlan plan;

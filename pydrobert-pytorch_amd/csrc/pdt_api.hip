@@ -55,6 +55,7 @@ const SwitchName kSwitchNames[] = {
     {"PDT_STEP_WIDE", &Switches::step_wide, 0},           {"PDT_CTC_LEAN_EXTRA", &Switches::ctc_lean_extra, 1},
     {"PDT_CTC_PAIR", &Switches::ctc_pair, 1},             {"PDT_STEP_FLAT", &Switches::step_flat, 1},
     {"PDT_CTC_STEADY", &Switches::ctc_steady, 1},         {"PDT_CTC_TWOFRAME", &Switches::ctc_twoframe, 1},
+    {"PDT_CTC_PACE", &Switches::ctc_pace, 1},
 };
 }  // namespace
 

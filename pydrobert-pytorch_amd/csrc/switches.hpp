@@ -20,6 +20,8 @@ struct Switches {
                        //                       else skip the lean tier's sort (0: every lean frame sorts; same kernel instance, same bits)
   int ctc_twoframe;    // PDT_CTC_TWOFRAME   1  ... at V = 256, W = 16: two steady frames of a producer pass decided at once, one per 16-lane row
                        //                       (0: frame by frame; same kernel instance, same bits; PDT_CTC_STEADY=0 implies 0)
+  int ctc_pace;        // PDT_CTC_PACE       1  CTC search, one-producer forms: a producer's issue priority steps down with its progress, so the
+                       //                       utterances of a launch end together (0: fixed priorities; same kernel instance, same bits)
 };
 
 Switches &switches();

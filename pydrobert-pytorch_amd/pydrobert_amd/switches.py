@@ -31,7 +31,7 @@ _HOST_DEFAULTS = {
 _NATIVE = (
     "PDT_LEV_BITPAR", "PDT_OC_BITPAR", "PDT_CTC_EXACT_DIV", "PDT_CTC_ROWREG", "PDT_STEP_WIDE",
     "PDT_CTC_LEAN_EXTRA", "PDT_CTC_PAIR", "PDT_STEP_FLAT", "PDT_CTC_STEADY",
-    "PDT_CTC_TWOFRAME",
+    "PDT_CTC_TWOFRAME", "PDT_CTC_PACE",
 )  # fmt: skip
 
 

@@ -990,6 +990,29 @@ int pdt_attn_pool_backward_elem(const int64_t *desc, int elem, const void *score
                                 const void *out, const void *lse, const void *grad_out, void *grad_score,
                                 void *grad_value, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The forward of pdt_attn_dot_elem on the matrix cores (csrc/attn_mfma.hip), for float16 / bfloat16 (elem 2, 3)
+ * self-attention shapes.  A descriptor qualifies when M >= 64; D and Dv are multiples of 16 in [32, 128]; the
+ * feature strides of query, key, value and out are 1; every row stride and T stride of query, key and value is a
+ * multiple of 8 elements and every row stride of out a multiple of 4.  out and lse have the layout and meaning
+ * above, so pdt_attn_dot_backward_elem takes them as they are; they are NOT the bits of pdt_attn_dot_elem: the
+ * probabilities are rounded to the element type once before they meet the values (scores, maximum and sum are
+ * float32), and a non-finite value in a frame that some rows of a 64-row block attend gives NaN in the rows that
+ * mask it (0 * inf in the matrix product, as in the reference's formula; a non-finite key there does not leak, and
+ * frames no row of the block attends are never read).
+ * pdt_attn_dot_mfma_plan (host only, no device work): 1 when the descriptor qualifies and the switch
+ *   PDT_ATTN_MFMA is not 0, else 0; a bad descriptor or element code gives the negative status.  On 1, plan7 =
+ *   rows per workgroup, rows per wave, frames per key block, spans of T, frames per span, workspace bytes,
+ *   dynamic LDS bytes; on 0 it is zeroed.
+ * pdt_attn_dot_mfma_elem: pdt_attn_dot_elem's arguments, everything checked before any launch.  A descriptor
+ *   that does not qualify (elem 0 and 1 included) is PDT_E_UNSUPPORTED whatever the switch says; query, key,
+ *   value or out not aligned to 16 bytes is PDT_E_ARG, as are null pointers, a missing scale and a workspace
+ *   smaller than the plan's. */
+int pdt_attn_dot_mfma_plan(const int64_t *desc, int elem, int64_t *plan7);
+
+int pdt_attn_dot_mfma_elem(const int64_t *desc, int elem, const void *query, const void *key, const void *value,
+                           const void *mask, const double *scale, void *out, void *lse, void *workspace,
+                           int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * The additive ("concat") attention score (reference _attn.py:344-361) with the two halves of W
  * applied by the caller: e[r, t] = sum_h v[h] * tanh(a[r, h] + b[group(r), t, h]), formed without

@@ -41,7 +41,7 @@
 // call on the exactly widened operands, each result rounded once where it is stored.  One place needs more
 // than that: the backward adds a group's row tiles into dK / dV, and the running sum may not pass through a
 // half element -- attn_bwd_half_kernel.
-#include "pdt_common.hpp"
+#include "attn_desc.hpp"
 
 #include <cmath>
 
@@ -57,44 +57,6 @@ static_assert(kAttnRows * kAttnFrames == kAttnThreads, "the softmax step gives e
 constexpr int kAttnRowsMaxD = 32;    // the one-thread-per-row forward: D, Dv up to this
 constexpr int64_t kAttnRowsGroup = 16;  // ... and at least this many rows per group
 constexpr int64_t kAttnLdsBytes = 57344;  // query / upstream tiles in LDS (plus the static state: under 64 KiB)
-
-enum { SQ = 0, SK, SV, SM, SO, SGQ, SGK, SGV, NSLOT };  // Q doubles as E, GQ as GE in the pool forms
-
-struct AttnDesc {
-  int64_t nd, R, G, M, T, D, Dv;
-  int64_t size[PDT_ATTN_MAX_DIMS];
-  int64_t st[NSLOT][PDT_ATTN_MAX_DIMS];
-  int64_t ts[NSLOT], fs[NSLOT];
-};
-
-struct AttnArgs {
-  AttnDesc d;
-  const void *q, *k, *v, *e;
-  const uint8_t *mask;
-  const void *out, *lse, *gout;
-  void *o, *l, *gq, *gk, *gv, *ge;
-  void *ws;
-  double scale;
-  int64_t rt;      // rows per tile
-  int64_t tiles;   // row tiles per group
-  int64_t splits;  // forward: spans of T; backward: frame chunks
-  int64_t span;    // frames per span (forward)
-};
-
-// element offsets of row r in every operand slot (row dims innermost last; static indexing only)
-__device__ __forceinline__ void attn_row_offsets(const AttnDesc &d, int64_t r, int64_t off[NSLOT]) {
-#pragma unroll
-  for (int s = 0; s < NSLOT; ++s) off[s] = 0;
-#pragma unroll
-  for (int i = PDT_ATTN_MAX_DIMS - 1; i >= 0; --i) {
-    if (i < d.nd) {
-      const int64_t n = d.size[i], idx = r % n;
-      r /= n;
-#pragma unroll
-      for (int s = 0; s < NSLOT; ++s) off[s] += idx * d.st[s][i];
-    }
-  }
-}
 
 template <typename F> __device__ __forceinline__ F wave_sum(F x) {
 #pragma unroll
@@ -798,11 +760,9 @@ template <typename E> __global__ __launch_bounds__(kAttnThreads) void attn_gq_co
 // ------------------------------------------------------------------------------------------
 // host side
 
-enum { ATTN_DOT = 0, ATTN_DOT_BWD = 1, ATTN_POOL = 2, ATTN_POOL_BWD = 3 };
-
 // Reads and checks the descriptor; the sizes must multiply to R = G * M, the innermost dims whose
 // sizes multiply to M (the group) must broadcast key, value and their gradients.
-static int attn_desc(const int64_t *in, int kind, AttnDesc *d) {
+int attn_desc(const int64_t *in, int kind, AttnDesc *d) {
   if (!in) return PDT_E_ARG;
   const bool pool = kind >= ATTN_POOL;
   d->nd = in[0]; d->R = in[1]; d->G = in[2]; d->M = in[3]; d->T = in[4]; d->D = in[5]; d->Dv = in[6];
@@ -908,6 +868,20 @@ template <typename E> static int attn_fwd_launch(AttnArgs &a, const AttnPlan &p,
     const int64_t n = a.d.R * a.d.Dv;
     if (n / kAttnThreads >= 0x7fffffffll) return PDT_E_TOO_LONG;
     hipLaunchKernelGGL(attn_fwd_combine_kernel<E>, dim3(attn_blocks(n, kAttnThreads)), blk, 0, s, a);
+  }
+  return (int)hipGetLastError();
+}
+
+// (for attn_mfma.hip, whose split partials have the format above)
+int attn_fwd_combine_launch(AttnArgs &a, int et, hipStream_t s) {
+  const int64_t n = a.d.R * a.d.Dv;
+  if (n / kAttnThreads >= 0x7fffffffll) return PDT_E_TOO_LONG;
+  const dim3 grid(attn_blocks(n, kAttnThreads)), blk(kAttnThreads);
+  switch (et) {
+    case 1: hipLaunchKernelGGL(attn_fwd_combine_kernel<double>, grid, blk, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(attn_fwd_combine_kernel<f16_t>, grid, blk, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(attn_fwd_combine_kernel<bf16_t>, grid, blk, 0, s, a); break;
+    default: hipLaunchKernelGGL(attn_fwd_combine_kernel<float>, grid, blk, 0, s, a); break;
   }
   return (int)hipGetLastError();
 }

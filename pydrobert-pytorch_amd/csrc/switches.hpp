@@ -22,6 +22,8 @@ struct Switches {
                        //                       (0: frame by frame; same kernel instance, same bits; PDT_CTC_STEADY=0 implies 0)
   int ctc_pace;        // PDT_CTC_PACE       1  CTC search, one-producer forms: a producer's issue priority steps down with its progress, so the
                        //                       utterances of a launch end together (0: fixed priorities; same kernel instance, same bits)
+  int attn_mfma;       // PDT_ATTN_MFMA      1  float16 / bfloat16 dot-product attention forward of self-attention shapes on the matrix cores
+                       //                       (attn_mfma.hip; 0: pdt_attn_dot_mfma_plan refuses every descriptor, so the tile kernels run)
 };
 
 Switches &switches();

@@ -11,11 +11,15 @@ cancels in the softmax.  ``ConcatSoftAttention`` applies the two halves of its `
 tensor; a subclass with its own ``score`` computes it with torch.  Either score then goes to
 ``pydrobert_amd::attention_pool`` for the masked softmax and the weighted sum.
 float16 / bfloat16 operands are read and written as they are (the ``_elem`` entry points: no float32 copy of any
-operand), computed in float32 and rounded once where a result is stored; ``lse`` is float32 for them.
+operand), computed in float32 and rounded once where a result is stored; ``lse`` is float32 for them.  Their
+self-attention shapes (64 or more rows sharing a key sequence, head dims that are multiples of 16 in [32, 128],
+16-byte-aligned rows) take the forward on the matrix cores (``csrc/attn_mfma.hip``; ``PDT_ATTN_MFMA=0``: never).
 CPU tensors, other dtypes and operands of mixed dtypes run the reference's formulas in torch.
 
 Deviation: a masked frame contributes exactly 0 on the HIP path, where the reference multiplies it by 0 (a
-non-finite key or value in a masked frame gives NaN there and not here).
+non-finite key or value in a masked frame gives NaN there and not here).  The matrix-core forward keeps this for
+keys and for frames that no row of a 64-row block attends; a non-finite value in a frame that only some of the
+block's rows mask gives NaN in those rows, as the reference does.
 """
 import abc
 from typing import List, Optional, Tuple
@@ -269,6 +273,21 @@ def _saved(out: torch.Tensor, lse: torch.Tensor, plan: _Plan, dtype: torch.dtype
     return out.detach().contiguous(), lse.detach().contiguous()
 
 
+def _mfma_workspace_bytes(plan: _Plan, dt: int, ops) -> int:
+    """The workspace bytes of the matrix-core forward where a dot-product call takes it, else -1: a half dtype, a
+    descriptor ``pdt_attn_dot_mfma_plan`` accepts (the switch PDT_ATTN_MFMA included) and query, key and value
+    pointers aligned to 16 bytes (out is allocated here)."""
+    if dt < 2:
+        return -1
+    plan7 = (_cabi.ctypes.c_int64 * 7)()
+    rc = _cabi.lib().pdt_attn_dot_mfma_plan(plan.desc.data_ptr(), dt, _cabi.ctypes.addressof(plan7))
+    if rc < 0:
+        _cabi.check(rc, "pdt_attn_dot_mfma_plan")
+    if rc != 1 or any(t.data_ptr() % 16 for t in ops[:3]):
+        return -1
+    return int(plan7[5])
+
+
 def _dot_geometry(query, key, value, mask, dim):
     if dim < 0 or dim > key.dim() - 2:
         raise RuntimeError("dot_attention takes a dim in [0, {}], got {}".format(key.dim() - 2, dim))
@@ -305,8 +324,19 @@ def _dot_attention_op(
         return out, lse
     if plan.T == 0:
         return out.zero_(), lse.fill_(-float("inf"))
-    ws = _workspace(plan, dt, _KIND_DOT, device)
     scale_c = _cabi.ctypes.c_double(scale)
+    mfma_ws = _mfma_workspace_bytes(plan, dt, ops)
+    if mfma_ws >= 0:  # (self-attention shapes in half: the matrix-core forward, csrc/attn_mfma.hip)
+        ws = torch.empty((max(1, mfma_ws),), device=device, dtype=torch.uint8)
+        with _cabi.on_device(device):
+            rc = _cabi.lib().pdt_attn_dot_mfma_elem(
+                plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[1].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]),
+                _cabi.ctypes.addressof(scale_c), out.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws.numel(),
+                _cabi.stream_ptr(device),
+            )  # fmt: skip
+        _cabi.check(rc, "pdt_attn_dot_mfma_elem")
+        return out, lse
+    ws = _workspace(plan, dt, _KIND_DOT, device)
     with _cabi.on_device(device):
         rc = _entry("pdt_attn_dot", dt)(
             plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[1].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]),

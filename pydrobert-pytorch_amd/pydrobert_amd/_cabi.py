@@ -39,7 +39,8 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # pdt_attn_pool_backward_elem: the five without the suffix keep refusing every dtype code but 0 and 1) and
 # SpecAugment's application (pdt_spec_augment_apply_elem, pdt_spec_augment_apply_warp_elem,
 # pdt_spec_augment_apply_backward_elem) with the host-only pdt_spec_augment_apply_form and
-# pdt_spec_augment_backward_workspace_bytes.
+# pdt_spec_augment_backward_workspace_bytes, and the attention forward on the matrix cores
+# (pdt_attn_dot_mfma_plan, pdt_attn_dot_mfma_elem).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -272,6 +273,8 @@ SIGNATURES = {
     ),
     "pdt_attn_pool_elem": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_attn_pool_backward_elem": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_attn_dot_mfma_plan": (_INT, [_P, _INT, _P]),
+    "pdt_attn_dot_mfma_elem": (_INT, [_P, _INT, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_concat_score_workspace_bytes": (_I64, [_P, _INT, _INT]),
     "pdt_concat_score_plan": (_INT, [_P, _INT, _P]),
     "pdt_concat_score": (_INT, [_P, _INT, _P, _P, _P, _P, _P]),

@@ -886,6 +886,19 @@ int attn_fwd_combine_launch(AttnArgs &a, int et, hipStream_t s) {
   return (int)hipGetLastError();
 }
 
+// (for attn_mfma_bwd.hip: delta of the rows into a.ws, by the kernel the launch below starts with)
+int attn_delta_launch(AttnArgs &a, int et, hipStream_t s) {
+  if (a.d.R / kAttnWaves >= 0x7fffffffll) return PDT_E_TOO_LONG;
+  const dim3 grid(attn_blocks(a.d.R, kAttnWaves)), blk(kAttnThreads);
+  switch (et) {
+    case 1: hipLaunchKernelGGL(attn_delta_kernel<double>, grid, blk, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(attn_delta_kernel<f16_t>, grid, blk, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(attn_delta_kernel<bf16_t>, grid, blk, 0, s, a); break;
+    default: hipLaunchKernelGGL(attn_delta_kernel<float>, grid, blk, 0, s, a); break;
+  }
+  return (int)hipGetLastError();
+}
+
 template <typename E> static int attn_bwd_launch(AttnArgs &a, const AttnPlan &p, bool pool, hipStream_t s) {
   const dim3 blk(kAttnThreads);
   if (a.d.R / kAttnWaves >= 0x7fffffffll) return PDT_E_TOO_LONG;

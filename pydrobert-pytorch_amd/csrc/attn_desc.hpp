@@ -1,5 +1,6 @@
-// What the attention translation units share (attn.hip, attn_mfma.hip): the descriptor as the kernels read it,
-// the kernel arguments, a row's element offsets, and the two host functions of attn.hip that attn_mfma.hip calls.
+// What the attention translation units share (attn.hip, attn_mfma.hip, attn_mfma_bwd.hip): the descriptor as the
+// kernels read it, the kernel arguments, a row's element offsets, and the host functions of attn.hip that the
+// matrix-core files call.
 #pragma once
 #include "pdt_common.hpp"
 
@@ -50,5 +51,7 @@ int attn_desc(const int64_t *in, int kind, AttnDesc *d);
 // attn.hip: launches attn_fwd_combine_kernel<E> over the split partials in a.ws (et: 2 f16_t, 3 bf16_t, 1 double,
 // else float)
 int attn_fwd_combine_launch(AttnArgs &a, int et, hipStream_t s);
+// attn.hip: launches attn_delta_kernel<E>: delta[r] = sum_c grad_out[r, c] * out[r, c] into a.ws (et as above)
+int attn_delta_launch(AttnArgs &a, int et, hipStream_t s);
 
 }  // namespace pdt

@@ -1,6 +1,6 @@
 // Dot-product attention forward on the matrix cores, for float16 / bfloat16 self-attention shapes:
 // groups of 64 or more rows, head dims D, Dv that are multiples of 16 in [32, 128].  A flash-attention walk on
-// v_mfma_f32_16x16x32_{f16,bf16}; the backward stays attn_bwd_half_kernel (attn.hip), fed by this out and lse.
+// v_mfma_f32_16x16x32_{f16,bf16}; the backward that reads this out and lse is attn_mfma_bwd.hip (§15).
 //
 // Work split.  A workgroup of four waves owns 64 consecutive rows of one group, a wave 16 of them, over a span of
 // T (all of T unless groups x row blocks cannot fill the chip: then spans leave the partials that attn.hip's
@@ -30,7 +30,7 @@
 // read.  A masked (row, frame) has its score replaced by -inf after the product (a non-finite key cannot leak) and
 // p = 0 exactly; a non-finite VALUE in a frame that other rows of the block attend reaches the rows that mask it as
 // 0 * inf = NaN through the matrix product -- the reference's own result, a deviation from the tile kernels.
-#include "attn_desc.hpp"
+#include "attn_mfma.hpp"
 #include "switches.hpp"
 
 #include <algorithm>
@@ -38,37 +38,7 @@
 
 namespace pdt {
 
-constexpr int kMfmaThreads = 256;
-constexpr int kMfmaWaveRows = 16;
-constexpr int kMfmaRows = 64;    // rows per workgroup
-constexpr int kMfmaFrames = 64;  // frames per key block
-constexpr int kMfmaPad = 8;      // halves of padding per LDS row
-constexpr int kMfmaVtPitch = kMfmaFrames + kMfmaPad;
-constexpr int kMfmaMinD = 32, kMfmaMaxD = 128;
-constexpr int64_t kMfmaMinRows = 64;
 constexpr int64_t kMfmaFill = 512;  // workgroups wanted before T is split: two per CU
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ f32x4 mfma_16x16x32(f16_t, u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x4 mfma_16x16x32(bf16_t, u32x4 a, u32x4 b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0,
-                                                 0);
-}
-
-// two float32 rounded to E (nearest even, elem_store's conversion), packed low element first
-template <typename E> __device__ __forceinline__ unsigned pack2(float lo, float hi) {
-  E e[2];
-  elem_store(&e[0], lo);
-  elem_store(&e[1], hi);
-  return (unsigned)__builtin_bit_cast(unsigned short, e[0]) | ((unsigned)__builtin_bit_cast(unsigned short, e[1]) << 16);
-}
 
 template <typename E> __global__ __launch_bounds__(kMfmaThreads) void attn_mfma_fwd_kernel(AttnArgs a) {
   extern __shared__ __align__(16) unsigned char mfma_smem[];
@@ -281,14 +251,7 @@ struct MfmaPlan {
 // 1: the descriptor takes the kernel above (plan filled), 0: it does not
 static int attn_mfma_plan(const AttnDesc &d, int elem, MfmaPlan *p) {
   *p = MfmaPlan{};
-  if (elem != 2 && elem != 3) return 0;
-  if (d.R == 0 || d.T < 1 || d.M < kMfmaMinRows) return 0;
-  if (d.D < kMfmaMinD || d.D > kMfmaMaxD || d.D % 16 || d.Dv < kMfmaMinD || d.Dv > kMfmaMaxD || d.Dv % 16) return 0;
-  if (d.fs[SQ] != 1 || d.fs[SK] != 1 || d.fs[SV] != 1 || d.fs[SO] != 1) return 0;
-  // 16-byte loads of query, key and value rows, 8-byte stores of out rows
-  if (d.ts[SQ] % 8 || d.ts[SK] % 8 || d.ts[SV] % 8) return 0;
-  for (int i = 0; i < d.nd; ++i)
-    if (d.st[SQ][i] % 8 || d.st[SK][i] % 8 || d.st[SV][i] % 8 || d.st[SO][i] % 4) return 0;
+  if (!attn_mfma_gate(d, elem)) return 0;
   p->tiles = (d.M + kMfmaRows - 1) / kMfmaRows;
   const int64_t blocks = d.G * p->tiles, frame_blocks = (d.T + kMfmaFrames - 1) / kMfmaFrames;
   // split T only when the rows cannot fill the chip, and never below two key blocks a span (a span pays for its

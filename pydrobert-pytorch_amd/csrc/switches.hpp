@@ -24,6 +24,8 @@ struct Switches {
                        //                       utterances of a launch end together (0: fixed priorities; same kernel instance, same bits)
   int attn_mfma;       // PDT_ATTN_MFMA      1  float16 / bfloat16 dot-product attention forward of self-attention shapes on the matrix cores
                        //                       (attn_mfma.hip; 0: pdt_attn_dot_mfma_plan refuses every descriptor, so the tile kernels run)
+  int attn_mfma_bwd;   // PDT_ATTN_MFMA_BWD  1  ... and its backward (attn_mfma_bwd.hip; 0: pdt_attn_dot_mfma_backward_plan refuses every descriptor,
+                       //                       so attn_bwd_half_kernel runs); apart from PDT_ATTN_MFMA: either pass reads the other's out and lse
 };
 
 Switches &switches();

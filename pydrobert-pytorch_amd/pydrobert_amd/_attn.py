@@ -13,7 +13,8 @@ tensor; a subclass with its own ``score`` computes it with torch.  Either score 
 float16 / bfloat16 operands are read and written as they are (the ``_elem`` entry points: no float32 copy of any
 operand), computed in float32 and rounded once where a result is stored; ``lse`` is float32 for them.  Their
 self-attention shapes (64 or more rows sharing a key sequence, head dims that are multiples of 16 in [32, 128],
-16-byte-aligned rows) take the forward on the matrix cores (``csrc/attn_mfma.hip``; ``PDT_ATTN_MFMA=0``: never).
+16-byte-aligned rows) take the forward on the matrix cores (``csrc/attn_mfma.hip``; ``PDT_ATTN_MFMA=0``: never) and
+the backward too (``csrc/attn_mfma_bwd.hip``; ``PDT_ATTN_MFMA_BWD=0``: never).
 CPU tensors, other dtypes and operands of mixed dtypes run the reference's formulas in torch.
 
 Deviation: a masked frame contributes exactly 0 on the HIP path, where the reference multiplies it by 0 (a
@@ -288,6 +289,21 @@ def _mfma_workspace_bytes(plan: _Plan, dt: int, ops) -> int:
     return int(plan7[5])
 
 
+def _mfma_bwd_workspace_bytes(plan: _Plan, dt: int, ops, grad_out) -> int:
+    """The workspace bytes of the matrix-core backward (``csrc/attn_mfma_bwd.hip``) where a dot-product call takes
+    it, else -1: as above with ``pdt_attn_dot_mfma_backward_plan`` (the switch PDT_ATTN_MFMA_BWD included) and
+    grad_out aligned to 16 bytes too (the gradients are allocated here)."""
+    if dt < 2:
+        return -1
+    plan5 = (_cabi.ctypes.c_int64 * 5)()
+    rc = _cabi.lib().pdt_attn_dot_mfma_backward_plan(plan.desc.data_ptr(), dt, _cabi.ctypes.addressof(plan5))
+    if rc < 0:
+        _cabi.check(rc, "pdt_attn_dot_mfma_backward_plan")
+    if rc != 1 or any(t.data_ptr() % 16 for t in list(ops[:3]) + [grad_out]):
+        return -1
+    return int(plan5[2])
+
+
 def _dot_geometry(query, key, value, mask, dim):
     if dim < 0 or dim > key.dim() - 2:
         raise RuntimeError("dot_attention takes a dim in [0, {}], got {}".format(key.dim() - 2, dim))
@@ -374,15 +390,21 @@ def _dot_attention_backward_op(
     gq = torch.empty(plan.out_shape[:-1] + [D], device=device, dtype=query.dtype)
     gk = torch.empty(plan.shared_shape + [D], device=device, dtype=query.dtype)
     gv = torch.empty(plan.shared_shape + [Dv], device=device, dtype=query.dtype)
-    ws = _workspace(plan, dt, _KIND_DOT_BWD, device)
     scale_c = _cabi.ctypes.c_double(scale)
+    mfma_ws = _mfma_bwd_workspace_bytes(plan, dt, ops, g)
+    if mfma_ws >= 0:  # (self-attention shapes in half: the matrix-core backward, csrc/attn_mfma_bwd.hip)
+        ws = torch.empty((max(1, mfma_ws),), device=device, dtype=torch.uint8)
+        entry, name = _cabi.lib().pdt_attn_dot_mfma_backward_elem, "pdt_attn_dot_mfma_backward_elem"
+    else:
+        ws = _workspace(plan, dt, _KIND_DOT_BWD, device)
+        entry, name = _entry("pdt_attn_dot_backward", dt), "pdt_attn_dot_backward"
     with _cabi.on_device(device):
-        rc = _entry("pdt_attn_dot_backward", dt)(
+        rc = entry(
             plan.desc.data_ptr(), dt, ops[0].data_ptr(), ops[1].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]),
             _cabi.ctypes.addressof(scale_c), out_c.data_ptr(), lse_c.data_ptr(), g.data_ptr(), gq.data_ptr(),
             gk.data_ptr(), gv.data_ptr(), ws.data_ptr(), ws.numel(), _cabi.stream_ptr(device),
         )  # fmt: skip
-    _cabi.check(rc, "pdt_attn_dot_backward")
+    _cabi.check(rc, name)
     q1_shape = list(query.unsqueeze(dim).shape)
     gq = _sum_to(gq.unsqueeze(dim), q1_shape).squeeze(dim)
     return gq.reshape(query.shape), _sum_to(gk, key.shape), _sum_to(gv, value.shape)

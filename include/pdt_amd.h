@@ -1013,6 +1013,28 @@ int pdt_attn_dot_mfma_elem(const int64_t *desc, int elem, const void *query, con
                            const void *mask, const double *scale, void *out, void *lse, void *workspace,
                            int64_t workspace_bytes, void *stream);
 
+/* The forward of pdt_attn_dot (float32) on the matrix cores (csrc/attn_mfma_f32.hip, v_mfma_f32_16x16x4_f32), for
+ * self-attention shapes.  A descriptor qualifies when M >= 64; D and Dv are multiples of 16 in [32, 128]; the feature
+ * strides of query, key, value and out are 1; every row stride and T stride of query, key and value and every row
+ * stride of out is a multiple of 4 elements.  out and lse have the layout and meaning above, so
+ * pdt_attn_dot_backward takes them as they are.  Products, maximum and sums are float32 and the probabilities are
+ * never rounded, so the result is inside pdt_attn_dot's error bound, though not its bits (another order of sums).
+ * As in the half forward above, a non-finite value in a frame that some rows of a 64-row block attend gives NaN in
+ * the rows that mask it; a non-finite key there does not leak, and frames no row of the block attends are never read.
+ * pdt_attn_dot_mfma_f32_plan (host only, no device work): 1 when the descriptor qualifies and the switch
+ *   PDT_ATTN_MFMA_F32 is not 0, else 0; a bad descriptor gives the negative status.  On 1, plan7 has the fields of
+ *   pdt_attn_dot_mfma_plan (the dynamic LDS bytes are 256 (D + Dv + 8): above 64 KiB at D = Dv = 128 only); on 0 it
+ *   is zeroed.
+ * pdt_attn_dot_mfma_f32: pdt_attn_dot's pointer arguments, everything checked before any launch.  A descriptor that
+ *   does not qualify is PDT_E_UNSUPPORTED whatever the switch says; query, key, value or out not aligned to 16 bytes
+ *   is PDT_E_ARG, as are null pointers (the mask may be null), a missing scale and a workspace smaller than the
+ *   plan's. */
+int pdt_attn_dot_mfma_f32_plan(const int64_t *desc, int64_t *plan7);
+
+int pdt_attn_dot_mfma_f32(const int64_t *desc, const void *query, const void *key, const void *value, const void *mask,
+                          const double *scale, void *out, void *lse, void *workspace, int64_t workspace_bytes,
+                          void *stream);
+
 /* The backward of pdt_attn_dot_backward_elem on the matrix cores (csrc/attn_mfma_bwd.hip), for the descriptors of
  * the forward above whose grad_out rows (out's layout) allow 16-byte loads (row strides of out multiples of 8) and
  * whose three gradient slots allow 8-byte stores (feature stride 1, every row and T stride a multiple of 4).  It

@@ -1,5 +1,6 @@
 // What the matrix-core attention kernels share (attn_mfma.hip: forward; attn_mfma_bwd.hip: backward,
-// §15): the tile constants, the vector types, the v_mfma_f32_16x16x32 wrappers, pack2 and the gate of both passes.
+// §15; attn_mfma_f32.hip: float32 forward, §16): the tile constants, the vector types, the v_mfma_f32_16x16x32 and
+// 16x16x4 wrappers, pack2 and the gates.
 #pragma once
 #include "attn_desc.hpp"
 
@@ -28,6 +29,12 @@ __device__ __forceinline__ f32x4 mfma_16x16x32(bf16_t, u32x4 a, u32x4 b, f32x4 c
                                                  0);
 }
 
+// v_mfma_f32_16x16x4_f32 (attn_mfma_f32.hip, §16): lane l gives A[l % 16][l / 16] and B[l / 16][l % 16], products and
+// sums in float32; the accumulator layout is that of the 16x16x32 forms
+__device__ __forceinline__ f32x4 mfma_16x16x4(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
 // two float32 rounded to E (nearest even, elem_store's conversion), packed low element first
 template <typename E> __device__ __forceinline__ unsigned pack2(float lo, float hi) {
   E e[2];
@@ -46,6 +53,18 @@ static inline bool attn_mfma_gate(const AttnDesc &d, int elem) {
   if (d.ts[SQ] % 8 || d.ts[SK] % 8 || d.ts[SV] % 8) return false;
   for (int i = 0; i < d.nd; ++i)
     if (d.st[SQ][i] % 8 || d.st[SK][i] % 8 || d.st[SV][i] % 8 || d.st[SO][i] % 4) return false;
+  return true;
+}
+
+// The gate of the float32 forward (attn_mfma_f32.hip): the same rows and head dims; 16-byte loads of query, key and
+// value rows and 16-byte stores of out rows are four elements here.
+static inline bool attn_mfma_f32_gate(const AttnDesc &d) {
+  if (d.R == 0 || d.T < 1 || d.M < kMfmaMinRows) return false;
+  if (d.D < kMfmaMinD || d.D > kMfmaMaxD || d.D % 16 || d.Dv < kMfmaMinD || d.Dv > kMfmaMaxD || d.Dv % 16) return false;
+  if (d.fs[SQ] != 1 || d.fs[SK] != 1 || d.fs[SV] != 1 || d.fs[SO] != 1) return false;
+  if (d.ts[SQ] % 4 || d.ts[SK] % 4 || d.ts[SV] % 4) return false;
+  for (int i = 0; i < d.nd; ++i)
+    if (d.st[SQ][i] % 4 || d.st[SK][i] % 4 || d.st[SV][i] % 4 || d.st[SO][i] % 4) return false;
   return true;
 }
 

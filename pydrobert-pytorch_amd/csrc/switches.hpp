@@ -26,6 +26,8 @@ struct Switches {
                        //                       (attn_mfma.hip; 0: pdt_attn_dot_mfma_plan refuses every descriptor, so the tile kernels run)
   int attn_mfma_bwd;   // PDT_ATTN_MFMA_BWD  1  ... and its backward (attn_mfma_bwd.hip; 0: pdt_attn_dot_mfma_backward_plan refuses every descriptor,
                        //                       so attn_bwd_half_kernel runs); apart from PDT_ATTN_MFMA: either pass reads the other's out and lse
+  int attn_mfma_f32;   // PDT_ATTN_MFMA_F32  1  float32 dot-product attention forward of self-attention shapes on the matrix cores
+                       //                       (attn_mfma_f32.hip; 0: pdt_attn_dot_mfma_f32_plan refuses every descriptor, so attn_fwd_kernel runs)
 };
 
 Switches &switches();

@@ -1059,6 +1059,32 @@ int pdt_attn_dot_mfma_backward_elem(const int64_t *desc, int elem, const void *q
                                     const void *lse, const void *grad_out, void *grad_query, void *grad_key,
                                     void *grad_value, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The backward of pdt_attn_dot_backward (float32) on the matrix cores (csrc/attn_mfma_f32_bwd.hip,
+ * v_mfma_f32_16x16x4_f32), for the descriptors of pdt_attn_dot_mfma_f32 whose grad_out rows (out's layout) allow
+ * 16-byte loads (row strides of out multiples of 4) and whose three gradient slots allow 16-byte stores (feature
+ * stride 1, every row and T stride a multiple of 4).  It reads only out and lse, whichever float32 forward wrote
+ * them.  Deterministic: no atomics, every gradient element summed in float32 by one lane and stored once; P and dS
+ * are never rounded, so the result is inside pdt_attn_dot_backward's error bound, though not its bits (another order
+ * of sums).  An all-masked row has grad_query exactly 0; a frame no row of its group attends has grad_key /
+ * grad_value exactly 0 whatever its key and value hold.  A non-finite key in a frame that some rows of a 64-row
+ * block attend reaches the rows that mask it as NaN in grad_query (0 * inf in the matrix product, the reference's
+ * result), a non-finite query or grad_out likewise in grad_key / grad_value.
+ * pdt_attn_dot_mfma_f32_backward_plan (host only): 1 when the descriptor qualifies and the switch
+ *   PDT_ATTN_MFMA_F32_BWD is not 0, else 0; a bad descriptor gives the negative status.  On 1, plan5 = rows per
+ *   workgroup (grad_query kernel), frames per workgroup (grad_key / grad_value kernel), workspace bytes (4 R),
+ *   dynamic LDS bytes of the first and of the second kernel (256 (D + Dv + 8) each: above 64 KiB at D = Dv = 128
+ *   only; the second kernel has 4624 static bytes besides); on 0 it is zeroed.
+ * pdt_attn_dot_mfma_f32_backward: pdt_attn_dot_mfma_backward_elem's arguments without elem, everything checked
+ *   before any launch.  A descriptor that does not qualify is PDT_E_UNSUPPORTED whatever the switch says; PDT_E_ARG
+ *   for a null pointer (the mask may be null), a missing scale, query, key, value, grad_out or a gradient not aligned
+ *   to 16 bytes, lse or workspace not aligned to 4, and a workspace smaller than the plan's. */
+int pdt_attn_dot_mfma_f32_backward_plan(const int64_t *desc, int64_t *plan5);
+
+int pdt_attn_dot_mfma_f32_backward(const int64_t *desc, const void *query, const void *key, const void *value,
+                                   const void *mask, const double *scale, const void *out, const void *lse,
+                                   const void *grad_out, void *grad_query, void *grad_key, void *grad_value,
+                                   void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * The additive ("concat") attention score (reference _attn.py:344-361) with the two halves of W
  * applied by the caller: e[r, t] = sum_h v[h] * tanh(a[r, h] + b[group(r), t, h]), formed without

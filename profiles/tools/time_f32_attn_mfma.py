@@ -7,6 +7,12 @@ settings alternating in one run on one device; every shape warmed first; min / m
 
   python profiles/tools/time_f32_attn_mfma.py [--windows 15] [--shapes hd64,hd128,hd64_n1] [--out FILE]
   python profiles/tools/time_f32_attn_mfma.py --errors [--out profiles/f32_attn_mfma_errors.json]
+  python profiles/tools/time_f32_attn_mfma.py --switch PDT_ATTN_MFMA_F32_BWD --passes forward_backward \
+      --out profiles/f32_attn_mfma_bwd_times.json
+
+--switch: the switch that alternates between 0 and 1 (every other one on its default): PDT_ATTN_MFMA_F32_BWD times the
+matrix-core backward (csrc/attn_mfma_f32_bwd.hip) against attn_bwd_kernel with the forward on
+the matrix cores under both settings; ``attention_gflop`` is the forward's either way.
 
 Shapes: causal self-attention over T = 1000 frames; hd64: N = 16, model 256, 4 heads; hd128: N = 16, model 1024,
 8 heads; hd64_n1: N = 1, model 256, 4 heads (few groups: T is split).  ``attention_gflop`` is the two matrix
@@ -50,7 +56,7 @@ def measure(args):
         b.synchronize()
         return a.elapsed_time(b) / calls
 
-    result = {"windows": args.windows, "device": torch.cuda.get_device_name(0), "shapes": {}}
+    result = {"switch": args.switch, "windows": args.windows, "device": torch.cuda.get_device_name(0), "shapes": {}}
     for name in args.shapes.split(","):
         T, N, model, H = SHAPES[name]
         d = model // H
@@ -74,16 +80,18 @@ def measure(args):
             m(leaf, leaf.unsqueeze(1), leaf.unsqueeze(1), mask).backward(gy)
 
         for p, fn in zip(PASSES, (fwd, fwd_bwd)):
+            if p not in args.passes.split(","):
+                continue
             calls, times = {}, {0: [], 1: []}
             for sw in (0, 1):  # warm-up, then the calls of a window of about 30 ms
-                with switches.override(PDT_ATTN_MFMA_F32=sw):
+                with switches.override(**{args.switch: sw}):
                     fn()
                     fn()
                     torch.cuda.synchronize()
                     calls[sw] = max(1, min(200, math.ceil(30.0 / max(window(fn, 3), 1e-3))))
             for _ in range(args.windows):
                 for sw in (0, 1):
-                    with switches.override(PDT_ATTN_MFMA_F32=sw):
+                    with switches.override(**{args.switch: sw}):
                         times[sw].append(window(fn, calls[sw]))
             rec = {}
             for sw in (0, 1):
@@ -151,6 +159,8 @@ def main():
     ap.add_argument("--windows", type=int, default=15)
     ap.add_argument("--shapes", default=",".join(SHAPES))
     ap.add_argument("--out", default=None)
+    ap.add_argument("--switch", default="PDT_ATTN_MFMA_F32")
+    ap.add_argument("--passes", default=",".join(PASSES))
     ap.add_argument("--errors", action="store_true")
     args = ap.parse_args()
     default = "f32_attn_mfma_errors.json" if args.errors else "f32_attn_mfma_times.json"

@@ -1,5 +1,5 @@
 // What the matrix-core attention kernels share (attn_mfma.hip: forward; attn_mfma_bwd.hip: backward,
-// §15; attn_mfma_f32.hip: float32 forward, §16): the tile constants, the vector types, the v_mfma_f32_16x16x32 and
+// §15; attn_mfma_f32.hip: float32 forward, §16; attn_mfma_f32_bwd.hip: float32 backward, §17): the tile constants, the vector types, the v_mfma_f32_16x16x32 and
 // 16x16x4 wrappers, pack2 and the gates.
 #pragma once
 #include "attn_desc.hpp"

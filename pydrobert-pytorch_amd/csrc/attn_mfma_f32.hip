@@ -1,7 +1,7 @@
 // Dot-product attention forward on the matrix cores for float32 self-attention shapes: groups of 64
 // or more rows, head dims D, Dv that are multiples of 16 in [32, 128].  A flash-attention walk of its own on
 // v_mfma_f32_16x16x4_f32: products and sums are float32, so P is never rounded and the result stays inside the
-// float32 bound of attn_fwd_kernel.  The backward that reads this out and lse is the unchanged attn_bwd_kernel.
+// float32 bound of attn_fwd_kernel.  The backward that reads this out and lse is attn_mfma_f32_bwd.hip (§17).
 //
 // Work split (that of attn_mfma.hip, §14, so plans, partials and the combine are shared).  A workgroup of four waves
 // owns 64 consecutive rows of one group, a wave 16 of them, over a span of T (all of T unless groups x row blocks

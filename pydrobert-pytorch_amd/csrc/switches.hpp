@@ -28,6 +28,8 @@ struct Switches {
                        //                       so attn_bwd_half_kernel runs); apart from PDT_ATTN_MFMA: either pass reads the other's out and lse
   int attn_mfma_f32;   // PDT_ATTN_MFMA_F32  1  float32 dot-product attention forward of self-attention shapes on the matrix cores
                        //                       (attn_mfma_f32.hip; 0: pdt_attn_dot_mfma_f32_plan refuses every descriptor, so attn_fwd_kernel runs)
+  int attn_mfma_f32_bwd;  // PDT_ATTN_MFMA_F32_BWD 1  ... and its backward (attn_mfma_f32_bwd.hip; 0: pdt_attn_dot_mfma_f32_backward_plan refuses every
+                          //                       descriptor, so attn_bwd_kernel runs); apart from PDT_ATTN_MFMA_F32: either pass reads the other's out and lse
 };
 
 Switches &switches();

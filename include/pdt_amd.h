@@ -1085,6 +1085,29 @@ int pdt_attn_dot_mfma_f32_backward(const int64_t *desc, const void *query, const
                                    const void *grad_out, void *grad_query, void *grad_key, void *grad_value,
                                    void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The forward of pdt_attn_dot (float32) for DECODE shapes, scores on the matrix cores (csrc/attn_mfma_dec.hip,
+ * v_mfma_f32_16x16x4_f32; the weighted sum on the vector unit).  A descriptor qualifies when 1 <= M <= 16; D and Dv
+ * are multiples of 16 in [64, 512]; the feature strides of query, key, value and out are 1; every row stride and T
+ * stride of query, key and value and every row stride of out is a multiple of 4 elements.  out and lse have the
+ * layout and meaning above, so pdt_attn_dot_backward takes them as they are.  The result is inside pdt_attn_dot's
+ * error bound, though not its bits (another order of sums).  The numbers contract is pdt_attn_dot's own, not the
+ * deviation of the two forwards above: a masked (row, frame) adds exactly 0 whatever key and value hold there, an
+ * all-masked row is NaN with lse (-inf, -inf), and two runs give the same bits.
+ * pdt_attn_dot_mfma_dec_plan (host only, no device work): 1 when the descriptor qualifies and the switch
+ *   PDT_ATTN_MFMA_DEC is not 0, else 0; a bad descriptor gives the negative status.  On 1, plan7 = columns of the
+ *   score tile (16, M padded), frames per wave (16), frames per key block (64), spans of T, frames per span, workspace
+ *   bytes (0 for one span, else spans * R * (Dv + 2) * 4: never more than pdt_attn_workspace_bytes reports for the
+ *   descriptor), dynamic LDS bytes (under 64 KiB); on 0 it is zeroed.
+ * pdt_attn_dot_mfma_dec: pdt_attn_dot's pointer arguments, everything checked before any launch.  A descriptor that
+ *   does not qualify is PDT_E_UNSUPPORTED whatever the switch says; query, key, value or out not aligned to 16 bytes
+ *   is PDT_E_ARG, as are null pointers (the mask may be null), a missing scale and a workspace smaller than the
+ *   plan's. */
+int pdt_attn_dot_mfma_dec_plan(const int64_t *desc, int64_t *plan7);
+
+int pdt_attn_dot_mfma_dec(const int64_t *desc, const void *query, const void *key, const void *value, const void *mask,
+                          const double *scale, void *out, void *lse, void *workspace, int64_t workspace_bytes,
+                          void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * The additive ("concat") attention score (reference _attn.py:344-361) with the two halves of W
  * applied by the caller: e[r, t] = sum_h v[h] * tanh(a[r, h] + b[group(r), t, h]), formed without

@@ -872,6 +872,12 @@ template <typename E> static int attn_fwd_launch(AttnArgs &a, const AttnPlan &p,
   return (int)hipGetLastError();
 }
 
+// (for attn_mfma_dec.hip: the allocator's figure for a float32 dot forward, which its plan may not exceed)
+int64_t attn_fwd_tile_ws_bytes(const AttnDesc &d) {
+  AttnPlan p;
+  return attn_plan(d, ATTN_DOT, 4, &p) == PDT_OK ? p.ws_bytes : 0;
+}
+
 // (for attn_mfma.hip, whose split partials have the format above)
 int attn_fwd_combine_launch(AttnArgs &a, int et, hipStream_t s) {
   const int64_t n = a.d.R * a.d.Dv;

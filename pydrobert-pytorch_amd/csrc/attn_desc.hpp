@@ -51,6 +51,9 @@ int attn_desc(const int64_t *in, int kind, AttnDesc *d);
 // attn.hip: launches attn_fwd_combine_kernel<E> over the split partials in a.ws (et: 2 f16_t, 3 bf16_t, 1 double,
 // else float)
 int attn_fwd_combine_launch(AttnArgs &a, int et, hipStream_t s);
+// attn.hip: the workspace bytes of the float32 dot forward on attn_fwd_kernel (what pdt_attn_workspace_bytes reports;
+// attn_mfma_dec.hip keeps its own partials within it)
+int64_t attn_fwd_tile_ws_bytes(const AttnDesc &d);
 // attn.hip: launches attn_delta_kernel<E>: delta[r] = sum_c grad_out[r, c] * out[r, c] into a.ws (et as above)
 int attn_delta_launch(AttnArgs &a, int et, hipStream_t s);
 

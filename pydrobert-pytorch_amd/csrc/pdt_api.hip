@@ -57,7 +57,7 @@ const SwitchName kSwitchNames[] = {
     {"PDT_CTC_STEADY", &Switches::ctc_steady, 1},         {"PDT_CTC_TWOFRAME", &Switches::ctc_twoframe, 1},
     {"PDT_CTC_PACE", &Switches::ctc_pace, 1},             {"PDT_ATTN_MFMA", &Switches::attn_mfma, 1},
     {"PDT_ATTN_MFMA_BWD", &Switches::attn_mfma_bwd, 1},   {"PDT_ATTN_MFMA_F32", &Switches::attn_mfma_f32, 1},
-    {"PDT_ATTN_MFMA_F32_BWD", &Switches::attn_mfma_f32_bwd, 1},
+    {"PDT_ATTN_MFMA_F32_BWD", &Switches::attn_mfma_f32_bwd, 1}, {"PDT_ATTN_MFMA_DEC", &Switches::attn_mfma_dec, 1},
 };
 }  // namespace
 

@@ -16,7 +16,9 @@ self-attention shapes (64 or more rows sharing a key sequence, head dims that ar
 16-byte-aligned rows) take the forward on the matrix cores (``csrc/attn_mfma.hip``; ``PDT_ATTN_MFMA=0``: never) and
 the backward too (``csrc/attn_mfma_bwd.hip``; ``PDT_ATTN_MFMA_BWD=0``: never).  The same shapes in float32 take a
 matrix-core forward of their own (``csrc/attn_mfma_f32.hip``; ``PDT_ATTN_MFMA_F32=0``: never) and a matrix-core
-backward of their own (``csrc/attn_mfma_f32_bwd.hip``; ``PDT_ATTN_MFMA_F32_BWD=0``: never).
+backward of their own (``csrc/attn_mfma_f32_bwd.hip``; ``PDT_ATTN_MFMA_F32_BWD=0``: never).  float32 decode shapes (1
+to 16 rows sharing a key sequence, head dims that are multiples of 16 in [64, 512]) take a forward with its scores on
+the matrix cores (``csrc/attn_mfma_dec.hip``; ``PDT_ATTN_MFMA_DEC=0``: never); their backward is the tile kernel's.
 CPU tensors, other dtypes and operands of mixed dtypes run the reference's formulas in torch.
 
 Deviation: a masked frame contributes exactly 0 on the HIP path, where the reference multiplies it by 0 (a
@@ -306,6 +308,21 @@ def _mfma_f32_workspace_bytes(plan: _Plan, dt: int, ops) -> int:
     return int(plan7[5])
 
 
+def _mfma_dec_workspace_bytes(plan: _Plan, dt: int, ops) -> int:
+    """The workspace bytes of the float32 decode forward (``csrc/attn_mfma_dec.hip``) where a dot-product call takes
+    it, else -1: float32, a descriptor ``pdt_attn_dot_mfma_dec_plan`` accepts (the switch PDT_ATTN_MFMA_DEC
+    included) and query, key and value pointers aligned to 16 bytes (out is allocated here)."""
+    if dt != 0:
+        return -1
+    plan7 = (_cabi.ctypes.c_int64 * 7)()
+    rc = _cabi.lib().pdt_attn_dot_mfma_dec_plan(plan.desc.data_ptr(), _cabi.ctypes.addressof(plan7))
+    if rc < 0:
+        _cabi.check(rc, "pdt_attn_dot_mfma_dec_plan")
+    if rc != 1 or any(t.data_ptr() % 16 for t in ops[:3]):
+        return -1
+    return int(plan7[5])
+
+
 def _mfma_bwd_workspace_bytes(plan: _Plan, dt: int, ops, grad_out) -> int:
     """The workspace bytes of the matrix-core backward (``csrc/attn_mfma_bwd.hip``) where a dot-product call takes
     it, else -1: as above with ``pdt_attn_dot_mfma_backward_plan`` (the switch PDT_ATTN_MFMA_BWD included) and
@@ -395,6 +412,17 @@ def _dot_attention_op(
                 _cabi.stream_ptr(device),
             )  # fmt: skip
         _cabi.check(rc, "pdt_attn_dot_mfma_f32")
+        return out, lse
+    mfma_ws = _mfma_dec_workspace_bytes(plan, dt, ops)
+    if mfma_ws >= 0:  # (decode shapes in float32, 1 to 16 rows a group: csrc/attn_mfma_dec.hip)
+        ws = torch.empty((max(1, mfma_ws),), device=device, dtype=torch.uint8)
+        with _cabi.on_device(device):
+            rc = _cabi.lib().pdt_attn_dot_mfma_dec(
+                plan.desc.data_ptr(), ops[0].data_ptr(), ops[1].data_ptr(), ops[2].data_ptr(), _cabi.ptr(ops[3]),
+                _cabi.ctypes.addressof(scale_c), out.data_ptr(), lse.data_ptr(), ws.data_ptr(), ws.numel(),
+                _cabi.stream_ptr(device),
+            )  # fmt: skip
+        _cabi.check(rc, "pdt_attn_dot_mfma_dec")
         return out, lse
     ws = _workspace(plan, dt, _KIND_DOT, device)
     with _cabi.on_device(device):

@@ -42,7 +42,8 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # pdt_spec_augment_backward_workspace_bytes, and the attention forward on the matrix cores
 # (pdt_attn_dot_mfma_plan, pdt_attn_dot_mfma_elem) and its backward (pdt_attn_dot_mfma_backward_plan,
 # pdt_attn_dot_mfma_backward_elem), and the float32 forward there (pdt_attn_dot_mfma_f32_plan,
-# pdt_attn_dot_mfma_f32) and its backward (pdt_attn_dot_mfma_f32_backward_plan, pdt_attn_dot_mfma_f32_backward).
+# pdt_attn_dot_mfma_f32) and its backward (pdt_attn_dot_mfma_f32_backward_plan, pdt_attn_dot_mfma_f32_backward),
+# and the float32 decode forward (pdt_attn_dot_mfma_dec_plan, pdt_attn_dot_mfma_dec).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -283,6 +284,8 @@ SIGNATURES = {
     ),
     "pdt_attn_dot_mfma_f32_plan": (_INT, [_P, _P]),
     "pdt_attn_dot_mfma_f32": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
+    "pdt_attn_dot_mfma_dec_plan": (_INT, [_P, _P]),
+    "pdt_attn_dot_mfma_dec": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_attn_dot_mfma_f32_backward_plan": (_INT, [_P, _P]),
     "pdt_attn_dot_mfma_f32_backward": (
         _INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],

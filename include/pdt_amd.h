@@ -1108,6 +1108,32 @@ int pdt_attn_dot_mfma_dec(const int64_t *desc, const void *query, const void *ke
                           const double *scale, void *out, void *lse, void *workspace, int64_t workspace_bytes,
                           void *stream);
 
+/* The backward of pdt_attn_dot_backward (float32) for DECODE shapes (csrc/attn_mfma_dec_bwd.hip): one kernel whose
+ * scores, dP, grad_key and grad_value are products on v_mfma_f32_16x16x4_f32 (grad_query on the vector unit), with
+ * delta computed inside it.  A descriptor qualifies when pdt_attn_dot_mfma_dec's does (grad_out has out's layout, so
+ * its rows allow 16-byte loads) and the three gradient slots have feature stride 1 and row and T strides that are
+ * multiples of 4.  It reads only out and lse, whichever float32 forward wrote them.  Deterministic, without atomics;
+ * grad_key and grad_value are stored once per element.  The result is inside pdt_attn_dot_backward's error bound,
+ * though not its bits, and the numbers contract is pdt_attn_dot_backward's own: a masked (row, frame) adds exactly 0
+ * to all three gradients whatever key and value hold there, an all-masked row has grad_query exactly 0, a frame no
+ * row of its group attends has grad_key / grad_value exactly 0 with its key and value unread.
+ * pdt_attn_dot_mfma_dec_backward_plan (host only): 1 when the descriptor qualifies and the switch
+ *   PDT_ATTN_MFMA_DEC_BWD is not 0, else 0; a bad descriptor gives the negative status.  On 1, plan5 = spans of T,
+ *   frames per span, workspace bytes (0 for one span, else the grad_query partials, spans * R * D * 4), dynamic LDS
+ *   bytes (above 64 KiB where D + Dv passes 888), the rows instance (4, 8 or 16: the least that covers M); on 0 it
+ *   is zeroed.
+ * pdt_attn_dot_mfma_dec_backward: pdt_attn_dot_mfma_f32_backward's arguments, everything checked before any launch.
+ *   A descriptor that does not qualify is PDT_E_UNSUPPORTED whatever the switch says; PDT_E_ARG for a null pointer
+ *   (the mask may be null; the workspace too where the plan needs none), a missing scale, query, key, value,
+ *   grad_out, a gradient or a needed workspace not aligned to 16 bytes, out or lse not aligned to 4, and a workspace
+ *   smaller than the plan's. */
+int pdt_attn_dot_mfma_dec_backward_plan(const int64_t *desc, int64_t *plan5);
+
+int pdt_attn_dot_mfma_dec_backward(const int64_t *desc, const void *query, const void *key, const void *value,
+                                   const void *mask, const double *scale, const void *out, const void *lse,
+                                   const void *grad_out, void *grad_query, void *grad_key, void *grad_value,
+                                   void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------
  * The additive ("concat") attention score (reference _attn.py:344-361) with the two halves of W
  * applied by the caller: e[r, t] = sum_h v[h] * tanh(a[r, h] + b[group(r), t, h]), formed without

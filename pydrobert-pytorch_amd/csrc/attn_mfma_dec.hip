@@ -48,13 +48,7 @@
 
 namespace pdt {
 
-constexpr int kDecRows = 16;             // the tile's columns: rows of a group, padded
-constexpr int kDecMinD = 64, kDecMaxD = 512;
-constexpr int64_t kDecFill = 512;        // workgroups wanted before T is split: two per CU
-constexpr int kDecQPad = 4;              // floats of padding per query row in LDS
-constexpr int kDecPPitch = 20;           // floats per frame of the P tile
 constexpr int kDecKAhead = 8;            // key chunks (sixteen features) a lane loads at once
-constexpr int kDecPFloats = kMfmaFrames * kDecPPitch;
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -333,18 +327,6 @@ template <int MR> __global__ __launch_bounds__(kMfmaThreads, 2) void attn_mfma_d
 
 // ------------------------------------------------------------------------------------------
 // host side
-
-// The gate: 1 to 16 rows a group, head dims of whole 16-column chunks in [64, 512], 16-byte loads of query, key and
-// value rows and 16-byte stores of out rows (four elements each).
-static bool attn_mfma_dec_gate(const AttnDesc &d) {
-  if (d.R == 0 || d.T < 1 || d.M < 1 || d.M > kDecRows) return false;
-  if (d.D < kDecMinD || d.D > kDecMaxD || d.D % 16 || d.Dv < kDecMinD || d.Dv > kDecMaxD || d.Dv % 16) return false;
-  if (d.fs[SQ] != 1 || d.fs[SK] != 1 || d.fs[SV] != 1 || d.fs[SO] != 1) return false;
-  if (d.ts[SQ] % 4 || d.ts[SK] % 4 || d.ts[SV] % 4) return false;
-  for (int i = 0; i < d.nd; ++i)
-    if (d.st[SQ][i] % 4 || d.st[SK][i] % 4 || d.st[SV][i] % 4 || d.st[SO][i] % 4) return false;
-  return true;
-}
 
 struct MfmaDecPlan {
   int64_t splits, span, ws_bytes, lds_bytes;

@@ -58,6 +58,7 @@ const SwitchName kSwitchNames[] = {
     {"PDT_CTC_PACE", &Switches::ctc_pace, 1},             {"PDT_ATTN_MFMA", &Switches::attn_mfma, 1},
     {"PDT_ATTN_MFMA_BWD", &Switches::attn_mfma_bwd, 1},   {"PDT_ATTN_MFMA_F32", &Switches::attn_mfma_f32, 1},
     {"PDT_ATTN_MFMA_F32_BWD", &Switches::attn_mfma_f32_bwd, 1}, {"PDT_ATTN_MFMA_DEC", &Switches::attn_mfma_dec, 1},
+    {"PDT_ATTN_MFMA_DEC_BWD", &Switches::attn_mfma_dec_bwd, 1},
 };
 }  // namespace
 
@@ -148,6 +149,8 @@ extern "C" {
 //     then: pdt_spec_augment_apply_elem, pdt_spec_augment_apply_warp_elem, pdt_spec_augment_apply_backward_elem
 //     (float16 / bfloat16 features as they are), pdt_spec_augment_apply_form and
 //     pdt_spec_augment_backward_workspace_bytes (host arithmetic only; no existing entry point changed)
+//     then: pdt_attn_dot_mfma_dec_backward_plan, pdt_attn_dot_mfma_dec_backward (csrc/attn_mfma_dec_bwd.hip) and
+//     the switch PDT_ATTN_MFMA_DEC_BWD (no existing entry point changed)
 int pdt_amd_abi_version(void) { return 14; }
 
 int pdt_amd_set_switch(const char *name, int value) {

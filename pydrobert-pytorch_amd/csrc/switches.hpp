@@ -33,6 +33,8 @@ struct Switches {
   int attn_mfma_dec;   // PDT_ATTN_MFMA_DEC  1  float32 dot-product attention forward of decode shapes (groups of 1 to 16 rows, head dims that are
                        //                       multiples of 16 in [64, 512]) with the scores on the matrix cores (attn_mfma_dec.hip; 0:
                        //                       pdt_attn_dot_mfma_dec_plan refuses every descriptor, so attn_fwd_kernel runs)
+  int attn_mfma_dec_bwd;  // PDT_ATTN_MFMA_DEC_BWD 1  ... and its backward (attn_mfma_dec_bwd.hip; 0: pdt_attn_dot_mfma_dec_backward_plan refuses every
+                          //                       descriptor, so attn_bwd_kernel runs); apart from PDT_ATTN_MFMA_DEC: it reads either forward's out and lse
 };
 
 Switches &switches();

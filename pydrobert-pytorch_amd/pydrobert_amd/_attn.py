@@ -18,7 +18,8 @@ the backward too (``csrc/attn_mfma_bwd.hip``; ``PDT_ATTN_MFMA_BWD=0``: never).  
 matrix-core forward of their own (``csrc/attn_mfma_f32.hip``; ``PDT_ATTN_MFMA_F32=0``: never) and a matrix-core
 backward of their own (``csrc/attn_mfma_f32_bwd.hip``; ``PDT_ATTN_MFMA_F32_BWD=0``: never).  float32 decode shapes (1
 to 16 rows sharing a key sequence, head dims that are multiples of 16 in [64, 512]) take a forward with its scores on
-the matrix cores (``csrc/attn_mfma_dec.hip``; ``PDT_ATTN_MFMA_DEC=0``: never); their backward is the tile kernel's.
+the matrix cores (``csrc/attn_mfma_dec.hip``; ``PDT_ATTN_MFMA_DEC=0``: never) and a one-kernel backward with its scores, grad_key
+and grad_value there (``csrc/attn_mfma_dec_bwd.hip``; ``PDT_ATTN_MFMA_DEC_BWD=0``: never).
 CPU tensors, other dtypes and operands of mixed dtypes run the reference's formulas in torch.
 
 Deviation: a masked frame contributes exactly 0 on the HIP path, where the reference multiplies it by 0 (a
@@ -354,6 +355,22 @@ def _mfma_f32_bwd_workspace_bytes(plan: _Plan, dt: int, ops, grad_out) -> int:
     return int(plan5[2])
 
 
+def _mfma_dec_bwd_workspace_bytes(plan: _Plan, dt: int, ops, grad_out) -> int:
+    """The workspace bytes of the float32 decode backward (``csrc/attn_mfma_dec_bwd.hip``) where a dot-product call
+    takes it, else -1: float32, a descriptor ``pdt_attn_dot_mfma_dec_backward_plan`` accepts (the switch
+    PDT_ATTN_MFMA_DEC_BWD included) and query, key, value and grad_out aligned to 16 bytes (the gradients are
+    allocated here)."""
+    if dt != 0:
+        return -1
+    plan5 = (_cabi.ctypes.c_int64 * 5)()
+    rc = _cabi.lib().pdt_attn_dot_mfma_dec_backward_plan(plan.desc.data_ptr(), _cabi.ctypes.addressof(plan5))
+    if rc < 0:
+        _cabi.check(rc, "pdt_attn_dot_mfma_dec_backward_plan")
+    if rc != 1 or any(t.data_ptr() % 16 for t in list(ops[:3]) + [grad_out]):
+        return -1
+    return int(plan5[2])
+
+
 def _dot_geometry(query, key, value, mask, dim):
     if dim < 0 or dim > key.dim() - 2:
         raise RuntimeError("dot_attention takes a dim in [0, {}], got {}".format(key.dim() - 2, dim))
@@ -464,6 +481,7 @@ def _dot_attention_backward_op(
     gv = torch.empty(plan.shared_shape + [Dv], device=device, dtype=query.dtype)
     scale_c = _cabi.ctypes.c_double(scale)
     mfma_ws, f32_ws = _mfma_bwd_workspace_bytes(plan, dt, ops, g), _mfma_f32_bwd_workspace_bytes(plan, dt, ops, g)
+    dec_ws = _mfma_dec_bwd_workspace_bytes(plan, dt, ops, g)
     elem = [dt]
     if mfma_ws >= 0:  # (self-attention shapes in half: the matrix-core backward, csrc/attn_mfma_bwd.hip)
         ws = torch.empty((max(1, mfma_ws),), device=device, dtype=torch.uint8)
@@ -471,6 +489,9 @@ def _dot_attention_backward_op(
     elif f32_ws >= 0:  # (... in float32: csrc/attn_mfma_f32_bwd.hip, an entry point without the element code)
         ws = torch.empty((max(1, f32_ws),), device=device, dtype=torch.uint8)
         entry, name, elem = _cabi.lib().pdt_attn_dot_mfma_f32_backward, "pdt_attn_dot_mfma_f32_backward", []
+    elif dec_ws >= 0:  # (decode shapes in float32: csrc/attn_mfma_dec_bwd.hip, one kernel and, with spans, a combine)
+        ws = torch.empty((max(1, dec_ws),), device=device, dtype=torch.uint8)
+        entry, name, elem = _cabi.lib().pdt_attn_dot_mfma_dec_backward, "pdt_attn_dot_mfma_dec_backward", []
     else:
         ws = _workspace(plan, dt, _KIND_DOT_BWD, device)
         entry, name = _entry("pdt_attn_dot_backward", dt), "pdt_attn_dot_backward"

@@ -43,7 +43,8 @@ LIB_PATH = os.environ.get("PDT_AMD_LIB", os.path.join(_HERE, "_lib", "libpdt_amd
 # (pdt_attn_dot_mfma_plan, pdt_attn_dot_mfma_elem) and its backward (pdt_attn_dot_mfma_backward_plan,
 # pdt_attn_dot_mfma_backward_elem), and the float32 forward there (pdt_attn_dot_mfma_f32_plan,
 # pdt_attn_dot_mfma_f32) and its backward (pdt_attn_dot_mfma_f32_backward_plan, pdt_attn_dot_mfma_f32_backward),
-# and the float32 decode forward (pdt_attn_dot_mfma_dec_plan, pdt_attn_dot_mfma_dec).
+# and the float32 decode forward (pdt_attn_dot_mfma_dec_plan, pdt_attn_dot_mfma_dec) and its backward
+# (pdt_attn_dot_mfma_dec_backward_plan, pdt_attn_dot_mfma_dec_backward).
 ABI_VERSION = 14
 
 PDT_OK = 0
@@ -288,6 +289,10 @@ SIGNATURES = {
     "pdt_attn_dot_mfma_dec": (_INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P]),
     "pdt_attn_dot_mfma_f32_backward_plan": (_INT, [_P, _P]),
     "pdt_attn_dot_mfma_f32_backward": (
+        _INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
+    ),
+    "pdt_attn_dot_mfma_dec_backward_plan": (_INT, [_P, _P]),
+    "pdt_attn_dot_mfma_dec_backward": (
         _INT, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _P],
     ),
     "pdt_concat_score_workspace_bytes": (_I64, [_P, _INT, _INT]),

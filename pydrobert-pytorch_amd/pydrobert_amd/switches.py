@@ -33,6 +33,7 @@ _NATIVE = (
     "PDT_CTC_LEAN_EXTRA", "PDT_CTC_PAIR", "PDT_STEP_FLAT", "PDT_CTC_STEADY",
     "PDT_CTC_TWOFRAME", "PDT_CTC_PACE", "PDT_ATTN_MFMA", "PDT_ATTN_MFMA_BWD",
     "PDT_ATTN_MFMA_F32", "PDT_ATTN_MFMA_F32_BWD", "PDT_ATTN_MFMA_DEC",
+    "PDT_ATTN_MFMA_DEC_BWD",
 )  # fmt: skip
 
 
